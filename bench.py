@@ -18,7 +18,18 @@ as `owner_routed`. `--mode weak` keeps 64M changes per GPU instead.
 Roofline: algorithmic bytes (48 B per change + 48 B per output cell) over the apply
 pipeline's device time (HIP events on the engine's stream). `traffic` = HBM bytes per apply from
 rocprofv3 PMC passes (FETCH_SIZE x 2 per the gfx950 correction, + WRITE_SIZE) that this script runs
-on itself, in child processes, before it touches the GPU.
+on itself, in child processes, before it touches the GPU (`--full` only).
+
+A plain run (`bench.py --gpus N --steps K --warmup W`) sets up, warms up, times the K steps and
+prints the headline line: `value`, `ms_per_step` and the roofline figures the timed steps' own HIP
+events give. `--full` adds every other figure, each from runs of its own after the timed steps:
+the live PMC traffic, the CPU baselines, steady state, the agent path and entry point, the
+H2D-inclusive apply, BLOB pks and config 5 (N = 1); per-rank PMC traffic, the CPU baseline, the
+exchange timed alone and the owner-routed merge (N > 1). `--no-pmc`, `--no-cpu-baseline` and
+`--no-config5` narrow a `--full` run.
+
+`--dump-outputs DIR` writes what the last timed step left its caller as DIR/<name>.npy (float64):
+the merged state's crsql_changes clock rows and per-site db_versions, see dump_outputs().
 
 Prints ONE JSON line (rank 0).
 """
@@ -205,6 +216,66 @@ def launch_ranks(n, script=None):
     return max(rcs, key=abs)
 
 
+# ---------------------------------------------------------------------------------- output dump
+DUMP_BUDGET = 48 << 20     # bytes of .npy data per run (the files of one run stay under 64 MB)
+DUMP_SEED = 0x5EED0D0C
+
+
+def dump_outputs(eng, outdir, prefix="", budget=DUMP_BUDGET):
+    """--dump-outputs: what the caller of the timed path holds after its last step -- the merged
+    state, as corro_state_export / corro_db_versions hand it over -- as float64 .npy files:
+
+      count.npy        [number of crsql_changes clock rows]
+      checksum.npy     per exported field (engine.ROW_FIELDS order) the wrapping 64-bit sum over ALL
+                       rows, as (upper, lower) 32-bit halves: any row order gives the same sums
+      db_versions.npy  per registered site, by ordinal
+      rows_<field>.npy a fixed sample of the clock rows, sorted by (table_cid, pk, ...): the rows
+                       whose seeded hash of (pk, table_cid) falls in the kept 1 / 2^k of the hash
+                       space (k the smallest that fits the budget), so two builds sample the same
+                       cells. A 64-bit field is stored as <field>_hi / <field>_lo, its upper and
+                       lower 32 bits, so every stored number is exact in float64.
+
+    The export's row order is unspecified; everything written is independent of it."""
+    import numpy as np
+    from corrosion_amd.engine import ROW_FIELDS
+    rows = eng.export()
+    rows.pop("long_values", None)
+    m = len(rows["pk"])
+    half = np.uint64(0xFFFFFFFF)
+
+    def split(a):
+        a = np.ascontiguousarray(a).view(np.uint64)
+        return (a >> np.uint64(32)).astype(np.float64), (a & half).astype(np.float64)
+
+    out = {"count": np.array([m], np.float64),
+           "db_versions": np.asarray(eng.db_versions()).astype(np.float64)}
+    sums = [np.array([rows[k].astype(np.uint64).sum(dtype=np.uint64)], np.uint64) for k in ROW_FIELDS]
+    out["checksum"] = np.array([[float(x[0]) for x in split(s)] for s in sums], np.float64)
+    per_row = 8 * sum(2 if np.dtype(dt).itemsize == 8 else 1 for dt in ROW_FIELDS.values())
+    k = 0
+    while (m >> k) * per_row > budget:
+        k += 1
+    if k:
+        h = (rows["pk"] * np.uint64(0x9E3779B97F4A7C15)) ^ (rows["table_cid"].astype(np.uint64) * np.uint64(0xBF58476D1CE4E5B9))
+        h = (h ^ (h >> np.uint64(29)) ^ np.uint64(DUMP_SEED)) * np.uint64(0x94D049BB133111EB)
+        keep = np.nonzero((h >> np.uint64(64 - k)) == 0)[0]
+    else:
+        keep = np.arange(m)
+    s = {f: rows[f][keep] for f in ROW_FIELDS}
+    order = np.lexsort((s["seq"], s["site"], s["db_version"], s["col_version"], s["pk"], s["table_cid"]))
+    order = order[: budget // per_row]
+    for f, dt in ROW_FIELDS.items():
+        a = s[f][order]
+        if np.dtype(dt).itemsize == 8:
+            out[f"rows_{f}_hi"], out[f"rows_{f}_lo"] = split(a)
+        else:
+            out[f"rows_{f}"] = a.astype(np.float64)
+    assert sum(a.nbytes for a in out.values()) <= 60 << 20
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(outdir, prefix + name + ".npy"), a)
+
+
 # ------------------------------------------------------------------------------------------ main
 def main():
     ap = argparse.ArgumentParser()
@@ -215,13 +286,20 @@ def main():
                     help="N=1: changes per apply (default 2^26); N>1 strong: global changes (default 2^29)")
     ap.add_argument("--mode", choices=("strong", "weak"), default="strong",
                     help="N>1: strong = config 3 (2^29 global, exchange timed); weak = 64M per GPU, owner-routed")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the live rocprofv3 traffic passes")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure (PMC traffic, CPU baselines, steady "
+                         "state, agent path, H2D, BLOB pks, config 5; N>1: exchange alone, owner-routed)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the state the last timed step left as DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-pmc", action="store_true", help="--full: skip the live rocprofv3 traffic passes")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--pmc-rank-child", type=int, default=0, help=argparse.SUPPRESS)  # world size emulated
     ap.add_argument("--pmc-c5-child", type=int, default=-1, help=argparse.SUPPRESS)  # 0 / 1: config 5 (impacts)
-    ap.add_argument("--no-config5", action="store_true", help="skip the config-5 figure of the N = 1 line")
+    ap.add_argument("--no-config5", action="store_true", help="--full: skip the config-5 figure of the N = 1 line")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.pmc_rank_child:
         run_rank_child(args, args.pmc_rank_child)
         return
@@ -236,16 +314,17 @@ def main():
         print(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world}; measuring {world} rank(s)", file=sys.stderr)
     rank = int(os.environ.get("RANK", "0"))
 
-    traffic, traffic_note, traffic_kern = None, "not measured (--no-pmc)", None
+    pmc = args.full and not args.no_pmc
+    traffic, traffic_note, traffic_kern = None, "not measured (--no-pmc)" if args.full else "not measured (--full)", None
     c5_traffic = {}
-    if world == 1 and not args.pmc_child and not args.no_pmc and rank == 0:
+    if world == 1 and not args.pmc_child and pmc and rank == 0:
         traffic, traffic_note, traffic_kern = pmc_traffic_live(args.changes or N_CHANGES)
         if not args.no_config5:
             for imp in (0, 1):
                 child = [os.path.abspath(__file__), "--pmc-c5-child", str(imp), "--steps", str(C5_PMC_APPLIES - 1)]
                 c5_traffic[imp] = pmc_traffic_live(N_C5, applies=C5_PMC_APPLIES, timeout=300, child_cmd=child)
 
-    if world > 1 and not args.no_pmc and rank == 0:
+    if world > 1 and pmc and rank == 0:
         # per-rank traffic of the step's local kernels, before this rank touches its GPU (the other
         # ranks wait in the process-group rendezvous meanwhile)
         G = (args.changes or N_GLOBAL_C3) if args.mode == "strong" else (args.changes or N_CHANGES) * world
@@ -422,7 +501,6 @@ def run_single(args, traffic, traffic_note, traffic_kern=None, c5_traffic=None):
         torch.cuda.synchronize()
         eng.close()
         return
-    cells = eng.count()
     kern = {}
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -432,6 +510,7 @@ def run_single(args, traffic, traffic_note, traffic_kern=None, c5_traffic=None):
             kern[k] = kern.get(k, 0.0) + v
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    cells = eng.count()        # of the state the last step left (every step leaves the same)
     kern = {k: v / args.steps for k, v in kern.items()}
     pipe_ms = sum(kern.values())
     alg_bytes = ALG_BYTES_PER_CHANGE * n + ALG_BYTES_PER_CELL * cells
@@ -439,18 +518,23 @@ def run_single(args, traffic, traffic_note, traffic_kern=None, c5_traffic=None):
     # (the fraction is over the whole step, reset included; the pipeline-only figure beside it)
     achieved = alg_bytes / (step_ms * 1e-3) / 1e9
     achieved_pipe = alg_bytes / (pipe_ms * 1e-3) / 1e9
-    steady = steady_state(eng, prep, n, dev, dt / args.steps * 1e3, cells)
-    agent = agent_path(eng, batch, n)
-    e2e_agent = agent_e2e(eng, batch, n, agent["ms"])
-    mixed_agent = agent_e2e_mixed(eng, batch, n, e2e_agent["ms"], reps=5)
-    e2e = host_batch_e2e(eng, batch, n)
-    cpu = None if args.no_cpu_baseline else cpu_baseline(batch)
+    if args.dump_outputs:
+        dump_outputs(eng, args.dump_outputs)
+    more = {}
+    if args.full:
+        more["steady_state"] = steady_state(eng, prep, n, dev, dt / args.steps * 1e3, cells)
+        agent = more["agent_path"] = agent_path(eng, batch, n)
+        e2e_agent = more["agent_e2e"] = agent_e2e(eng, batch, n, agent["ms"])
+        more["agent_e2e_mixed"] = agent_e2e_mixed(eng, batch, n, e2e_agent["ms"], reps=5)
+        more["end_to_end_h2d"] = host_batch_e2e(eng, batch, n)
+        more["cpu_baseline"] = None if args.no_cpu_baseline else cpu_baseline(batch)
     eng.close()
     del batch, prep
-    torch.cuda.empty_cache()
-    blob = blob_pk_figures(dt / args.steps * 1e3)
-    torch.cuda.empty_cache()
-    c5 = None if args.no_config5 else config5_figures(3, c5_traffic or {})
+    if args.full:
+        torch.cuda.empty_cache()
+        more["blob_pk"] = blob_pk_figures(dt / args.steps * 1e3)
+        torch.cuda.empty_cache()
+        more["config5"] = None if args.no_config5 else config5_figures(3, c5_traffic or {})
     line = {
         "metric": METRIC,
         "value": n / dt * args.steps,
@@ -477,15 +561,11 @@ def run_single(args, traffic, traffic_note, traffic_kern=None, c5_traffic=None):
                      "pipeline_achieved": achieved_pipe, "pipeline_frac": achieved_pipe / HBM_PEAK_GBS,
                      "alg_bytes_per_apply": alg_bytes, "pipeline_ms": pipe_ms, "kernels_ms": kern,
                      "dominant": max(kern, key=kern.get)},
-        "cpu_baseline": cpu,
-        "steady_state": steady,
-        "agent_path": agent,
-        "agent_e2e": e2e_agent,
-        "agent_e2e_mixed": mixed_agent,
-        "end_to_end_h2d": e2e,
-        "blob_pk": blob,
-        "config5": c5,
     }
+    for k in ("cpu_baseline", "steady_state", "agent_path", "agent_e2e", "agent_e2e_mixed", "end_to_end_h2d", "blob_pk",
+              "config5"):
+        if k in more:
+            line[k] = more[k]
     print(json.dumps(line), flush=True)
 
 
@@ -844,24 +924,28 @@ def run_multi(args, world, rank, pmc=(None, "not measured (--no-pmc)", None)):
         step()
     barrier()
     dt = time.perf_counter() - t0
-    for _ in range(max(1, args.steps // 2)):
-        mine = exchange_only()
-    barrier()
-    # owner-routed: the received batch IS this rank's owner-routed ingest; merge it alone
-    prep = eng.prepare(mine)
-    eng.reset()
-    eng.apply_prepared(prep)
-    barrier()
-    t1 = time.perf_counter()
-    for _ in range(args.steps):
+    cells_t = torch.tensor([eng.count()], device=sdev, dtype=torch.int64)
+    if args.dump_outputs:
+        dump_outputs(eng, args.dump_outputs, prefix=f"rank{rank}_", budget=DUMP_BUDGET // world)
+    dt_own = 0.0
+    if args.full:
+        for _ in range(max(1, args.steps // 2)):
+            mine = exchange_only()
+        barrier()
+        # owner-routed: the received batch IS this rank's owner-routed ingest; merge it alone
+        prep = eng.prepare(mine)
         eng.reset()
         eng.apply_prepared(prep)
-    barrier()
-    dt_own = time.perf_counter() - t1
-    stats = torch.tensor([dt, dt_own, sum(ex_ms) / max(1, len(ex_ms))], device=sdev, dtype=torch.float64)
+        barrier()
+        t1 = time.perf_counter()
+        for _ in range(args.steps):
+            eng.reset()
+            eng.apply_prepared(prep)
+        barrier()
+        dt_own = time.perf_counter() - t1
+    stats =torch.tensor([dt, dt_own, sum(ex_ms) / max(1, len(ex_ms))], device=sdev, dtype=torch.float64)
     dist.all_reduce(stats, op=dist.ReduceOp.MAX)
     dt, dt_own, exm = (float(x) for x in stats.tolist())
-    cells_t = torch.tensor([eng.count()], device=sdev, dtype=torch.int64)
     dist.all_reduce(cells_t, op=dist.ReduceOp.SUM)
     cells = int(cells_t.item())
     if rank == 0:
@@ -883,7 +967,6 @@ def run_multi(args, world, rank, pmc=(None, "not measured (--no-pmc)", None)):
                 "traffic_by_kernel_per_rank": ({k: {"fetch": round(v["fetch"]), "write": round(v["write"])}
                                                 for k, v in sorted(pmc[2].items())} if pmc[2] else None),
                 "alg_bytes_per_step": alg, "exchange_bytes_per_step": moved, "cells": cells}
-        cpu = None if args.no_cpu_baseline else cpu_baseline_sample(npk)
         line = {
             "metric": METRIC,
             "value": G / dt * args.steps,
@@ -905,18 +988,19 @@ def run_multi(args, world, rank, pmc=(None, "not measured (--no-pmc)", None)):
                        "total_changes": G, "changes_per_gpu": n_local,
                        "parallelism": f"pk-hash x{world}, {backend} all-to-all"},
             "roofline": roof,
-            "cpu_baseline": cpu,
-            "exchange_ms": exm,
             "exchange": {"form": "stream-ordered slots: partition into fixed slots of cap records per destination, "
                                  "counts + slots in two equal-split all-to-alls on the engine's stream, mapped merge "
                                  "skipping the padding; no host wait between partition and merge",
                          "slot_cap": cap, "slot_padding": cap * world / max(1, n_local) - 1.0,
-                         "overflowed_steps": int(sum(1 for o in overflows if o)),
-                         "exchange_ms_note": "exchange_ms = the exact-size exchange timed alone (partition + "
-                                             "counts + all-to-all-v + unpack, host-synchronised)"},
-            "owner_routed": {"value": G / dt_own * args.steps, "ms_per_step": dt_own / args.steps * 1e3,
-                             "note": "each rank merges only its own rows (the received batch), no collective"},
+                         "overflowed_steps": int(sum(1 for o in overflows if o))},
         }
+        if args.full:
+            line["cpu_baseline"] = None if args.no_cpu_baseline else cpu_baseline_sample(npk)
+            line["exchange_ms"] = exm
+            line["exchange"]["exchange_ms_note"] = ("exchange_ms = the exact-size exchange timed alone (partition + "
+                                                    "counts + all-to-all-v + unpack, host-synchronised)")
+            line["owner_routed"] = {"value": G / dt_own * args.steps, "ms_per_step": dt_own / args.steps * 1e3,
+                                    "note": "each rank merges only its own rows (the received batch), no collective"}
         print(json.dumps(line), flush=True)
     eng.close()
     dist.destroy_process_group()

@@ -8,9 +8,9 @@
 # Steps:
 #   smoke      __graft_entry__.smoke()
 #   tests      every -m gpu test (TESTS= narrows it, e.g. TESTS="tests/test_gpu_agent_device.py")
-#   bench      python bench.py (defaults: config 2, live PMC traffic, cpu baseline)
+#   bench      python bench.py --full (config 2 with every figure: live PMC traffic, cpu baseline, ...)
 #   multi2     the N > 1 line rehearsed with 2 gloo ranks on the one GPU (2^26 global changes)
-#   quick      python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-pmc
+#   quick      python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-pmc
 #   trace      kernel trace + stats of a short bench run (gpurun_out/$OUT/trace)
 #   pmc        FETCH_SIZE / WRITE_SIZE / SQ groups over a short bench run, one pass each
 #   c5 / c5imp config 5 at 64M (no impacts / with impacts), live PMC traffic (SIZES= overrides)
@@ -24,7 +24,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}" || exit 1
 export TMPDIR=/tmp
 OUT="gpurun_out/${OUT:-run}"
 mkdir -p "$OUT"
-B="python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-pmc"
+B="python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-pmc"
 C5="python tools/bench_config5.py --sizes ${SIZES:-64000000} --reps 3"
 SY="python bench_sync.py --steps 3 --warmup 1 --cpu-sample 1000"
 
@@ -42,8 +42,8 @@ for s in "$@"; do
   case $s in
     smoke) step smoke 300 python -u -c "import __graft_entry__ as g; g.smoke()" ;;
     tests) step tests 1100 python -u -m pytest ${TESTS:-tests} -m gpu -x -q --timeout 300 --timeout-method thread ;;
-    bench) step bench 600 python -u bench.py ;;
-    multi2) CORRO_BENCH_BACKEND=gloo step multi2 600 python -u bench.py --gpus 2 --changes $((1 << 26)) --steps 3 --warmup 1 ;;
+    bench) step bench 600 python -u bench.py --full ;;
+    multi2) CORRO_BENCH_BACKEND=gloo step multi2 600 python -u bench.py --full --gpus 2 --changes $((1 << 26)) --steps 3 --warmup 1 ;;
     quick) step quick 300 $B ;;
     trace) step trace 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o run -- $B
            kstats "$OUT/trace" ;;

@@ -1,5 +1,5 @@
-"""A/B of environment knobs on the config-2 bench: each setting runs `bench.py` (quick: no CPU
-baseline, no PMC passes) in a child process, twice, alternating, and one line per run is printed
+"""A/B of environment knobs on the config-2 bench: each setting runs `bench.py --full` (quick: no
+CPU baseline, no PMC passes) in a child process, twice, alternating, and one line per run is printed
 with ms_per_step and the agent figures. Settings: AB="CORRO_HIST_U=8 CORRO_HIST_U=16;CORRO_SCAT_U=8"
 (settings separated by ';', variables inside a setting by spaces; an empty setting = defaults)."""
 import json
@@ -15,7 +15,7 @@ def run(setting):
     for kv in setting.split():
         k, v = kv.split("=", 1)
         env[k] = v
-    cmd = [sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "3",
+    cmd = [sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--full", "--steps", "10", "--warmup", "3",
            "--no-cpu-baseline", "--no-pmc"]
     out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=400)
     if out.returncode != 0:
