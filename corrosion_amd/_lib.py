@@ -41,6 +41,7 @@ EXPORTS = [
     "corro_booked_insert_db_batch", "corro_affinity_of_type", "corro_table_set_affinity", "corro_set_affinity_policy",
     "corro_ctx_metrics", "corro_table_committed", "corro_ctx_track_touched", "corro_state_export_touched",
     "corro_ctx_set_store_limit", "corro_partition_var", "corro_unpack_var",
+    "corro_values_compact", "corro_ctx_set_values_autocompact",
 ]
 
 CORRO_CS_FULL, CORRO_CS_EMPTY, CORRO_CS_EMPTY_SET = 0, 1, 2
@@ -189,6 +190,8 @@ def lib():
         "corro_state_export_touched": (i32, [vp, C.POINTER(Rows), u64, vp]),
         "corro_ctx_track_touched": (i32, [vp, i32]),
         "corro_ctx_set_store_limit": (i32, [vp, u64]),
+        "corro_values_compact": (i32, [vp, i32, vp, vp, vp]),
+        "corro_ctx_set_values_autocompact": (i32, [vp, u64]),
         "corro_state_reset": (i32, [vp]),
         "corro_db_versions": (i32, [vp, vp, u32]),
         "corro_compute_needs": (i32, [vp, C.POINTER(SyncEntries), i32, C.POINTER(NeedsOut), i32]),

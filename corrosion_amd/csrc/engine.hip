@@ -524,6 +524,7 @@ static int store_clear(corro_ctx *ctx) {
     ctx->state_total = 0;
     ctx->state_rows = 0;
     ctx->arena_top = 0;
+    ctx->vc_last_bytes = 0;
     ctx->state_epoch++;
     ctx->poisoned = false;
     return CORRO_OK;
@@ -1173,6 +1174,16 @@ int corro_apply_batch(corro_ctx *ctx, const corro_changes *in, int mem, corro_ap
     if (in->n == 0) return CORRO_OK;
     if (fault_armed("apply")) return fail(CORRO_E_NOMEM, "injected fault (CORRO_FAULT): apply");
     const auto t0 = std::chrono::steady_clock::now();
+    // auto-compaction of the value arena (corro_ctx_set_values_autocompact), before the batch's long
+    // values are appended and before any merge write: no handle is held across this point (the
+    // batch names its bytes by val_off into its own val_data; corro_process_multiple_changes' batch,
+    // spans and buffered rows live in the agent's scratch and the bookie's host bytes). The threshold
+    // doubles with the live size, so the copies amortise to O(1) per ingested byte. Out of memory:
+    // skipped (the arena only stays larger); a device error is the apply's.
+    if (ctx->vc_min_bytes && ctx->arena_top >= std::max<uint64_t>(ctx->vc_min_bytes, 2 * ctx->vc_last_bytes)) {
+        const int crc = values_compact(ctx, false, in->val_off ? in->val_data_len + 8 : 0, nullptr, nullptr, nullptr);
+        if (crc != CORRO_OK && crc != CORRO_E_NOMEM) return crc;
+    }
     ctx->apply_wrote = false;
     const int rc = apply_batch_impl(ctx, in, mem, out);
     if (rc != CORRO_OK && ctx->apply_wrote) {

@@ -133,6 +133,11 @@ int pk_keys_device(corro_ctx *ctx, uint32_t table, const PkRefs &r, uint64_t n, 
 bool pk_canonical(const uint8_t *p, uint64_t len, std::string &out, bool *single_int, int64_t *ival);
 std::string pack_int_pk(int64_t v);
 
+// The value arena rewritten to the union of its live spans (values_compact.hip; corro_values_compact's
+// body). `reserve`: room for that many more bytes in the new buffer (an apply about to append).
+int values_compact(corro_ctx *ctx, bool dry_run, uint64_t reserve, uint64_t *live_bytes, uint64_t *arena_before,
+                   uint64_t *arena_after);
+
 // the rocPRIM kernels' first-use cost paid once per process and device (prims.hip)
 int prims_warm(corro_ctx *ctx);
 // the agent's pinned host areas for a call of `ncs` changesets (agent_dev.hip), ahead of the first call
@@ -201,8 +206,10 @@ struct corro_ctx {
     bool state_wide = false;      // some clock row holds a non-INTEGER value
     corro::DevBuf d_defer, d_relist;  // deferred buckets of a merge round, the re-merge list
     corro::DevBuf d_dense, d_dense_ts, d_dense_view;  // materialised state (extraction), its pseudo-buckets
-    corro::DevBuf d_arena;        // long TEXT/BLOB value bytes (append-only; handles point into it)
+    corro::DevBuf d_arena;        // long TEXT/BLOB value bytes (append-only between compactions; handles point into it)
     uint64_t arena_top = 0;       // bytes in use
+    uint64_t vc_min_bytes = 0;    // corro_ctx_set_values_autocompact (0: off)
+    uint64_t vc_last_bytes = 0;   // arena_top after the last compaction (0: none since the reset)
     uint64_t dense_epoch = ~0ULL;
 
     // per-batch scratch

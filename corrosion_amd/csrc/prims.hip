@@ -69,6 +69,13 @@ int prim_inclusive_max_u64(void *temp, size_t *temp_bytes, const uint64_t *in, u
     return CORRO_OK;
 }
 
+// inclusive sum of u64 (the value compaction's dead bytes before each run); temp == nullptr -> *temp_bytes = size needed
+int prim_inclusive_sum_u64(void *temp, size_t *temp_bytes, const uint64_t *in, uint64_t *out, uint64_t n, hipStream_t s) {
+    const hipError_t e = rocprim::inclusive_scan(temp, *temp_bytes, in, out, (size_t)n, rocprim::plus<uint64_t>(), s);
+    if (e != hipSuccess) return fail(CORRO_E_DEVICE, std::string("scan: ") + hipGetErrorString(e));
+    return CORRO_OK;
+}
+
 struct OvfMax {
     __device__ inline uint32_t operator()(uint32_t x, uint32_t y) const { return x > y ? x : y; }
 };

@@ -306,6 +306,20 @@ class MergeEngine:
     def set_store_limit(self, max_heap_records):
         L.check(L.lib().corro_ctx_set_store_limit(self._h, int(max_heap_records)))
 
+    def compact_values(self, dry_run=False):
+        """Compact the long-value arena on the device (corro_values_compact): the bytes no present clock
+        row names are dropped and every handle is rewritten, so handles taken before the call are
+        invalid after it. dry_run only measures. Returns {"live_bytes", "arena_before", "arena_after"}."""
+        live, before, after = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        L.check(L.lib().corro_values_compact(self._h, 1 if dry_run else 0, C.byref(live), C.byref(before),
+                                             C.byref(after)))
+        return {"live_bytes": live.value, "arena_before": before.value, "arena_after": after.value}
+
+    def set_values_autocompact(self, min_bytes):
+        """Compact the arena at an apply's entry once it holds min_bytes and twice what the previous
+        compaction left (corro_ctx_set_values_autocompact; 0 = off). Handles then die at the next apply."""
+        L.check(L.lib().corro_ctx_set_values_autocompact(self._h, int(min_bytes)))
+
     def value_bytes(self, handles):
         """Bytes of long values by their handles (the val1 of rows with val_len == VAL_LONG)."""
         h = np.ascontiguousarray(handles, dtype=np.uint64)

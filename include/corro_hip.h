@@ -261,9 +261,30 @@ int corro_db_versions(corro_ctx *ctx, int64_t *out, uint32_t nsites);
  * is CORRO_VAL_LONG; a handle's low 24 bits are its length). Value i's bytes go to
  * bytes[out_off[i], out_off[i+1]); out_off holds n + 1 entries (host). CORRO_E_RANGE if cap <
  * out_off[n] (out_off is still filled), CORRO_E_INVALID for a handle outside the arena. Handles stay
- * valid until corro_state_reset. */
+ * valid until corro_state_reset, corro_values_compact or, with auto-compaction on
+ * (corro_ctx_set_values_autocompact), the next apply: resolve them before any of these. */
 int corro_value_bytes(corro_ctx *ctx, const uint64_t *handles, uint64_t n, uint8_t *bytes, uint64_t cap,
                       uint64_t *out_off);
+
+/* Compact the long-value arena on the device: the bytes that no present clock row names (values
+ * that lost their merge or were overwritten since) are dropped, the union of the live byte spans is
+ * copied into a fresh buffer (spans that several rows share, or that overlap, are kept once) and
+ * every row's handle is rewritten. The merged state is otherwise unchanged; handles taken before the
+ * call are invalid after it. The out pointers are optional: *live_bytes = the size of the union,
+ * *arena_before / *arena_after = corro_metrics.arena_bytes around the call (after = live rounded up
+ * to 8). dry_run != 0 only measures: *live_bytes is set, nothing moves, *arena_after = *arena_before.
+ * An empty state is a no-op; an arena with no live value drops to 0 bytes.
+ * Failure atomicity: a failure before the handles are rewritten (allocation, scratch) leaves the
+ * state, the arena and every handle as they were; a device error at or after the rewrite poisons the
+ * context. A poisoned context refuses the call with CORRO_E_DEVICE. */
+int corro_values_compact(corro_ctx *ctx, int dry_run, uint64_t *live_bytes, uint64_t *arena_before,
+                         uint64_t *arena_after);
+/* Auto-compaction policy (0 = off, the default): corro_apply_batch -- and with it every call that
+ * applies through it, corro_process_multiple_changes included -- compacts at its entry, before the
+ * batch's values are appended, when arena_bytes >= max(min_bytes, 2 * arena_bytes after the previous
+ * compaction): amortised O(1) work per ingested byte. A compaction that cannot get its memory is
+ * skipped and the apply proceeds; a device error fails the apply. */
+int corro_ctx_set_values_autocompact(corro_ctx *ctx, uint64_t min_bytes);
 
 /* Stage timing with HIP events recorded on the engine's stream (for roofline reporting).
  * corro_last_timings returns milliseconds of the last apply per stage:
@@ -285,8 +306,8 @@ typedef struct {
     uint64_t state_rows, state_records;   /* now */
     uint64_t max_batch;        /* largest batch (chunk_size) */
     double apply_seconds;      /* wall time inside corro_apply_batch */
-    uint64_t arena_bytes;      /* long-value arena in use: append-only (every batch's TEXT/BLOB values
-                                  longer than 16 bytes, winners or not) until corro_state_reset, at most
+    uint64_t arena_bytes;      /* long-value arena in use: appended to (every batch's TEXT/BLOB values
+                                  longer than 16 bytes, winners or not) until corro_state_reset or a compaction, at most
                                   2^40 bytes (CORRO_E_RANGE beyond) */
     uint64_t aff_sensitive;    /* changes converted by a column affinity whose stored value may differ
                                   between SQLite versions (TEXT <-> REAL rounding), under
