@@ -481,6 +481,7 @@ static int ctx_prepare_device(corro_ctx *ctx) {
         return fail(CORRO_E_NO_DEVICE, std::string("libcorro_hip is built for gfx950, device is ") + prop.gcnArchName);
     CORRO_HIP_TRY(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
     CORRO_HIP_TRY(hipHostMalloc((void **)&ctx->h_misc, MISC_WORDS * sizeof(uint64_t), hipHostMallocDefault));
+    CORRO_HIP_TRY(hipHostGetDevicePointer((void **)&ctx->h_misc_dev, ctx->h_misc, 0));
     for (auto &e : ctx->ev) CORRO_HIP_TRY(hipEventCreate(&e));
     const size_t lds_max = 160 * 1024;
     for (const void *f : {(const void *)k_hist<8>, (const void *)k_hist<16>, (const void *)k_hist<32>,
@@ -515,11 +516,17 @@ static int store_alloc(corro_ctx *ctx, uint64_t capacity_hint) {
 
 static int store_clear(corro_ctx *ctx) {
     hipStream_t s = ctx->stream;
-    CORRO_HIP_TRY(hipMemsetAsync(ctx->d_ent.p, 0, ((size_t)ctx->B << ctx->log2S) * sizeof(RowEnt), s));
-    CORRO_HIP_TRY(hipMemsetAsync(ctx->d_used.p, 0, ctx->B * 4ULL, s));
-    CORRO_HIP_TRY(hipMemsetAsync(ctx->d_gen.p, 0, ctx->B * 4ULL, s));
-    CORRO_HIP_TRY(hipMemsetAsync(ctx->d_heap_top.p, 0, 8, s));  // (stream-ordered before the next apply)
-    if (ctx->d_touch_n.p) CORRO_HIP_TRY(hipMemsetAsync(ctx->d_touch_n.p, 0, 8, s));
+    // (one launch, stream-ordered before the next apply)
+    const size_t n16 = ((size_t)ctx->B << ctx->log2S) * (sizeof(RowEnt) / 16);
+    // (A/B knobs: workgroups, non-temporal stores)
+    static const uint32_t grid_max = std::getenv("CORRO_CLEAR_GRID") ? (uint32_t)std::atoi(std::getenv("CORRO_CLEAR_GRID")) : CLEAR_GRID;
+    // (non-temporal: the zeros are not read back soon, and written through they leave the batch's columns
+    // in the Infinity Cache for k_hist: 0.143 -> 0.112 ms at config 2)
+    static const bool nt = !std::getenv("CORRO_CLEAR_NT") || std::atoi(std::getenv("CORRO_CLEAR_NT")) != 0;
+    const uint32_t grid = (uint32_t)std::min<size_t>(std::max(grid_max, 1u), (n16 + CLEAR_T - 1) / CLEAR_T);
+    hipLaunchKernelGGL(nt ? k_store_clear<true> : k_store_clear<false>, dim3(std::max(grid, 1u)), dim3(CLEAR_T), 0, s,
+                       row_store(ctx), ctx->B, ctx->d_touch_n.as<unsigned long long>());
+    CORRO_HIP_TRY(hipGetLastError());
     ctx->touch_bound = 0;
     ctx->state_total = 0;
     ctx->state_rows = 0;
@@ -670,6 +677,7 @@ int corro_ctx_create(const corro_table_desc *tables, uint32_t ntables, uint64_t 
     if (!rc) rc = ctx->d_stage_off.ensure(B * 4ULL);
     if (!rc) rc = ctx->d_bflags.ensure(((B + 31) / 32) * 4ULL);
     if (!rc) rc = ctx->d_misc.ensure(MISC_WORDS * 8);
+    if (!rc) rc = ctx->d_colscan.ensure((1 + (B + COLSCAN_T - 1) / COLSCAN_T) * 8ULL);
     if (!rc) rc = ctx->d_ovf_list.ensure(B * 4ULL);
     if (!rc) rc = ctx->d_gen_list.ensure(3 * B * 4ULL);
     if (!rc) rc = ctx->d_wide_list.ensure(B * 4ULL);
@@ -712,7 +720,7 @@ void corro_ctx_destroy(corro_ctx *ctx) {
                       &ctx->d_heap, &ctx->d_heap_ts, &ctx->d_heap_top, &ctx->d_stride, &ctx->d_defer,
                       &ctx->d_relist, &ctx->d_dense, &ctx->d_dense_ts, &ctx->d_dense_view, &ctx->d_in,
                       &ctx->d_hist, &ctx->d_new_cnt, &ctx->d_stage_off, &ctx->d_bflags, &ctx->d_stage,
-                      &ctx->d_misc, &ctx->d_ovf_list, &ctx->d_gen_list, &ctx->d_wide_list, &ctx->d_fast_of, &ctx->d_ovf_sort, &ctx->d_ovf_rcl, &ctx->d_ovf_sum, &ctx->d_ovf_plan, &ctx->d_setdbv,
+                      &ctx->d_misc, &ctx->d_colscan, &ctx->d_ovf_list, &ctx->d_gen_list, &ctx->d_wide_list, &ctx->d_fast_of, &ctx->d_ovf_sort, &ctx->d_ovf_rcl, &ctx->d_ovf_sum, &ctx->d_ovf_plan, &ctx->d_setdbv,
                       &ctx->d_scan_tmp, &ctx->d_impact, &ctx->d_export, &ctx->d_needs, &ctx->d_needs1,
                       &ctx->d_xidx, &ctx->d_xout, &ctx->d_wire, &ctx->d_wire_schema, &ctx->d_wire_sites,
                       &ctx->d_ncols, &ctx->d_part, &ctx->d_arena, &ctx->d_aff, &ctx->d_affflag,
@@ -909,9 +917,12 @@ static int apply_chunk(corro_ctx *ctx, BatchDev bd, uint8_t *imp_buf) {
 
     TRY(ctx->d_hist.ensure((size_t)ntiles * B * 4));
     TRY(ctx->d_stage.ensure((size_t)n * sizeof(Rec)));
-    // (bucket general bits, misc counters and per-site db_version maxima are zeroed by k_hist)
+    // (bucket general bits, misc counters, per-site db_version maxima and k_colscan's ticket and status
+    // words are zeroed by k_hist)
+    const uint32_t scan_wgs = (B + COLSCAN_T - 1) / COLSCAN_T;
     ApplyZero z{ctx->d_bflags.as<uint32_t>(), ctx->d_misc.as<unsigned long long>(),
-                ctx->d_dbv_batch.as<unsigned long long>(), (B + 31) / 32, (uint32_t)MISC_WORDS, nsites};
+                ctx->d_dbv_batch.as<unsigned long long>(), (B + 31) / 32, (uint32_t)MISC_WORDS, nsites,
+                ctx->d_colscan.as<unsigned long long>(), 1 + scan_wgs};
     // (0: every body stores only the nonzero flags -- in Zipf-hot batches most changes are no-ops,
     // and each flag store is a random byte)
     if (imp_buf) CORRO_HIP_TRY(hipMemsetAsync(imp_buf, 0, bd.ap ? ctx->pm_n : n, s));
@@ -934,15 +945,16 @@ static int apply_chunk(corro_ctx *ctx, BatchDev bd, uint8_t *imp_buf) {
                        ctx->d_hist.as<uint32_t>(), z);
     CORRO_HIP_TRY(hipGetLastError());
     mark(1);
-    hipLaunchKernelGGL(k_colscan, dim3((B + 255) / 256), dim3(256), 0, s, ctx->d_hist.as<uint32_t>(), ntiles, B,
-                       ctx->d_new_cnt.as<uint32_t>());
+    // (bucket totals and their exclusive scan in one kernel: its time is reported in the k_colscan
+    // slot, the k_plan slot stays 0 and its event is not recorded)
+    hipLaunchKernelGGL(k_colscan, dim3(scan_wgs), dim3(COLSCAN_T), 0, s, ctx->d_hist.as<uint32_t>(), ntiles, B,
+                       ctx->d_new_cnt.as<uint32_t>(), ctx->d_stage_off.as<uint32_t>(),
+                       ctx->d_colscan.as<unsigned long long>());
     mark(2);
-    hipLaunchKernelGGL(k_plan, dim3(1), dim3(1024), 0, s, ctx->d_new_cnt.as<uint32_t>(), B,
-                       ctx->d_stage_off.as<uint32_t>());
-    mark(3);
+    // (no value words, types or lengths: every value is an INTEGER, so k_scatter never sets MISC_WIDE)
+    const bool plain = !bd.v1 && !bd.vt && !bd.vl && !bd.conv;
     {
         static const bool nt_stores = std::getenv("CORRO_HIP_NT") && std::atoi(std::getenv("CORRO_HIP_NT")) != 0;
-        const bool plain = !bd.v1 && !bd.vt && !bd.vl && !bd.conv;
         if (bd.ts_v1 && !plain) return fail(CORRO_E_INVALID, "internal: ts_v1 on a batch with value words");
         static const bool scat8 = std::getenv("CORRO_SCAT_U") && std::atoi(std::getenv("CORRO_SCAT_U")) == 8;  // A/B knob
         auto kern = plain ? (nt_stores ? k_scatter<true, true> : scat8 ? k_scatter<true, false, 8> : k_scatter<true, false>)
@@ -954,7 +966,7 @@ static int apply_chunk(corro_ctx *ctx, BatchDev bd, uint8_t *imp_buf) {
                            (uint32_t)ctx->tables.size(), misc);
     }
     CORRO_HIP_TRY(hipGetLastError());
-    mark(4);
+    mark(3);
 
     MergeArgs a{};
     a.stage = ctx->d_stage.as<Rec>();
@@ -1008,9 +1020,14 @@ static int apply_chunk(corro_ctx *ctx, BatchDev bd, uint8_t *imp_buf) {
         if (ctx->h_misc[0]) return error_from_bits(ctx->h_misc[0]);
     }
     bool extra_rounds = false;
+    // k_triage queues a bucket for the mixed-type fast body only when the state or the batch holds a
+    // non-INTEGER value: a plain batch into an INTEGER state leaves that queue empty, so its kernel
+    // is not launched
+    const bool wide_possible = ctx->state_wide || !plain;
     for (int round = 0;; round++) {
         if (round > 40) return fail(CORRO_E_NOMEM, "internal: the row store did not take the batch's rows");
-        mark(4);
+        // (ev[3] closes the scatter and opens the first round unless the host waited in between)
+        if (round > 0 || a.impact) mark(4);
         // triage in one pass, queue appends per wave (k_triage); the fast body's workgroups skip it
         static const bool no_triage = std::getenv("CORRO_TRIAGE") && std::atoi(std::getenv("CORRO_TRIAGE")) == 0;
         if (!no_triage) {
@@ -1026,11 +1043,13 @@ static int apply_chunk(corro_ctx *ctx, BatchDev bd, uint8_t *imp_buf) {
             auto kern = packed ? k_merge_fast_int<true, true> : k_merge_fast_int<true, false>;
             hipLaunchKernelGGL(kern, dim3(nblocks), dim3(FAST_T), 0, s, a);
             CORRO_HIP_TRY(hipGetLastError());
-            hipLaunchKernelGGL(k_merge_fast_wide<true>, dim3(std::min(nblocks, LIST_GRID)), dim3(FAST_T), 0, s, a);
+            if (wide_possible)
+                hipLaunchKernelGGL(k_merge_fast_wide<true>, dim3(std::min(nblocks, LIST_GRID)), dim3(FAST_T), 0, s, a);
         } else {
             hipLaunchKernelGGL(k_merge_fast_int<false>, dim3(nblocks), dim3(FAST_T), 0, s, a);
             CORRO_HIP_TRY(hipGetLastError());
-            hipLaunchKernelGGL(k_merge_fast_wide<false>, dim3(std::min(nblocks, LIST_GRID)), dim3(FAST_T), 0, s, a);
+            if (wide_possible)
+                hipLaunchKernelGGL(k_merge_fast_wide<false>, dim3(std::min(nblocks, LIST_GRID)), dim3(FAST_T), 0, s, a);
         }
         CORRO_HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(k_merge_gen_small, dim3(std::min(nblocks, 4 * LIST_GRID)), dim3(GEN_SMALL_THREADS), 0, s, a);
@@ -1040,24 +1059,25 @@ static int apply_chunk(corro_ctx *ctx, BatchDev bd, uint8_t *imp_buf) {
         hipLaunchKernelGGL(k_merge_gen, dim3(std::min(nblocks, LIST_GRID)), dim3(MERGE_THREADS), 0, s, a);
         CORRO_HIP_TRY(hipGetLastError());
         mark(5);
-        if (round == 0) {
-            hipLaunchKernelGGL(k_dbv_fold, dim3((nsites + 255) / 256), dim3(256), 0, s,
-                               ctx->d_dbv.as<unsigned long long>(), ctx->d_dbv_batch.as<unsigned long long>(), nsites,
-                               (const unsigned long long *)misc);
-            CORRO_HIP_TRY(hipMemsetAsync(misc + MISC_ROWS, 0, 8, s));
-            hipLaunchKernelGGL(k_sum_used, dim3(1), dim3(1024), 0, s, ctx->d_used.as<uint32_t>(), B, misc);
+        if (round == 0) {  // (the db_version fold, the region fill sum and the host's copy of misc)
+            hipLaunchKernelGGL(k_apply_tail, dim3(1), dim3(TAIL_T), 0, s, ctx->d_dbv.as<unsigned long long>(),
+                               ctx->d_dbv_batch.as<unsigned long long>(), nsites, ctx->d_used.as<uint32_t>(), B, misc,
+                               ctx->h_misc_dev);
+            CORRO_HIP_TRY(hipGetLastError());
+        } else {
+            CORRO_HIP_TRY(hipMemcpyAsync(ctx->h_misc, misc, MISC_WORDS * 8, hipMemcpyDeviceToHost, s));
         }
-        CORRO_HIP_TRY(hipMemcpyAsync(ctx->h_misc, misc, MISC_WORDS * 8, hipMemcpyDeviceToHost, s));
         CORRO_HIP_TRY(hipStreamSynchronize(s));
         if (round == 0) {
             if (ctx->h_misc[0]) return error_from_bits(ctx->h_misc[0]);  // (nothing merged)
             ctx->apply_wrote = true;  // from here on a failure leaves the state part-merged
             if (prof)
-                for (int i = 0; i < 4; i++) CORRO_HIP_TRY(hipEventElapsedTime(&ctx->last_ms[i], ctx->ev[i], ctx->ev[i + 1]));
+                for (int i = 0; i < 3; i++)  // (k_hist, k_colscan, k_scatter; the k_plan slot stays 0)
+                    CORRO_HIP_TRY(hipEventElapsedTime(&ctx->last_ms[i == 2 ? 3 : i], ctx->ev[i], ctx->ev[i + 1]));
         }
         if (prof) {
             float ms = 0.f;
-            CORRO_HIP_TRY(hipEventElapsedTime(&ms, ctx->ev[4], ctx->ev[5]));
+            CORRO_HIP_TRY(hipEventElapsedTime(&ms, ctx->ev[round > 0 || a.impact ? 4 : 3], ctx->ev[5]));
             merge_ms += ms;
         }
         const uint64_t novf = ctx->h_misc[MISC_OVF];
@@ -1091,9 +1111,10 @@ static int apply_chunk(corro_ctx *ctx, BatchDev bd, uint8_t *imp_buf) {
         ctx->last_ms[5] = ovf_ms;
     }
     if (extra_rounds) {  // the overflow fold / deferred rounds changed the region fills
-        CORRO_HIP_TRY(hipMemsetAsync(misc + MISC_ROWS, 0, 8, s));
-        hipLaunchKernelGGL(k_sum_used, dim3(1), dim3(1024), 0, s, ctx->d_used.as<uint32_t>(), B, misc);
-        CORRO_HIP_TRY(hipMemcpyAsync(ctx->h_misc, misc, MISC_WORDS * 8, hipMemcpyDeviceToHost, s));
+        hipLaunchKernelGGL(k_apply_tail, dim3(1), dim3(TAIL_T), 0, s, ctx->d_dbv.as<unsigned long long>(),
+                           ctx->d_dbv_batch.as<unsigned long long>(), 0u, ctx->d_used.as<uint32_t>(), B, misc,
+                           ctx->h_misc_dev);
+        CORRO_HIP_TRY(hipGetLastError());
         CORRO_HIP_TRY(hipStreamSynchronize(s));
     }
     ctx->state_total += ctx->h_misc[MISC_LIVE];  // (a signed delta in two's complement)

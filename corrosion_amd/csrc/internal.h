@@ -218,6 +218,7 @@ struct corro_ctx {
     corro::DevBuf d_new_cnt, d_stage_off, d_bflags;
     corro::DevBuf d_stage;        // staged Recs
     corro::DevBuf d_misc;         // counters (merge_kernels.h MISC_*)
+    corro::DevBuf d_colscan;      // k_colscan: ticket + one status word per workgroup (u64)
     corro::DevBuf d_ovf_list;     // overflow buckets
     corro::DevBuf d_gen_list;     // buckets queued for the general body
     corro::DevBuf d_wide_list;    // buckets queued for the mixed-type fast body
@@ -285,7 +286,8 @@ struct corro_ctx {
     corro::DevBuf d_hdr_stage;       // their device copy + the device known outcomes
     uint64_t agent_ncs = 0;       // changesets of the current call (d_agent_spans column length)
     uint64_t agent_nbatch_max = 0;  // input changes of the current call (bound on the applied batch)
-    uint64_t *h_misc = nullptr;   // pinned, 16 words
+    uint64_t *h_misc = nullptr;   // pinned, MISC_WORDS words
+    unsigned long long *h_misc_dev = nullptr;  // its device address (k_apply_tail writes it)
     uint32_t *h_ovf = nullptr;    // pinned, 3 B + 16 words: the overflow fold's readbacks (run_overflow)
     // stage timing
     bool profiling = false;

@@ -5,8 +5,9 @@
 //   k_hist     tile-local LDS histogram of the (table, pk) bucket of every change (reads pk and
 //              table_cid only); one coalesced row of counts per tile (no global atomics).
 //   k_colscan  per bucket, exclusive prefix over tiles -> each tile owns a disjoint slice of the
-//              bucket (deterministic slices, no atomics).
-//   k_plan     one workgroup: bucket slice offsets for the staged batch and the next state.
+//              bucket (deterministic slices, no atomics); and the bucket slice offsets for the
+//              staged batch (the exclusive scan of the bucket totals, by a look-back across its
+//              workgroups: there is no separate plan kernel).
 //   k_scatter  re-read the SoA batch, stage each change as one 64-B record in its bucket slice;
 //              per-bucket "general" bits, per-site crsql_db_versions maxima, input validation
 //              (unknown cid / site, out-of-range encodings).
@@ -205,11 +206,14 @@ __device__ inline uint32_t site_rank_of(const MergeArgs &a, uint32_t site) {
 // schema has one table (every change's bucket then uses table 0; k_scatter does the same and
 // reports a bad table id as an error).
 // The per-apply words the scatter and merge accumulate into (bucket general bits, misc counters,
-// per-site db_version maxima) are zeroed here too: three fills fewer per apply.
+// per-site db_version maxima, k_colscan's ticket and status words) are zeroed here too: four fills
+// fewer per apply.
 struct ApplyZero {
     uint32_t *bflags;
     unsigned long long *misc, *dbv_batch;
     uint32_t nbflags, nmisc, nsites;
+    unsigned long long *scan;  // k_colscan: [0] ticket, [1 + w] status of workgroup w
+    uint32_t nscan;
 };
 // SLOT: slot mode (corro_apply_slots) -- its own instantiation, so the SoA form keeps every load of a
 // lane's HIST_U changes issued before the first use (a slot-mode branch inside that loop cost the
@@ -227,6 +231,7 @@ k_hist(BatchDev in, uint32_t tile, uint32_t log2B, uint32_t one_table, uint32_t 
         for (uint32_t i = t; i < z.nbflags; i += nt) z.bflags[i] = 0;
         for (uint32_t i = t; i < z.nmisc; i += nt) z.misc[i] = 0;
         for (uint32_t i = t; i < z.nsites; i += nt) z.dbv_batch[i] = 0;
+        for (uint32_t i = t; i < z.nscan; i += nt) z.scan[i] = 0;
     }
     for (uint32_t i = threadIdx.x; i < B; i += blockDim.x) hist[i] = 0;
     bool sover = false;
@@ -267,86 +272,78 @@ k_hist(BatchDev in, uint32_t tile, uint32_t log2B, uint32_t one_table, uint32_t 
     for (uint32_t b = threadIdx.x; b < B; b += blockDim.x) row[b] = hist[b];
 }
 
-// per bucket: exclusive prefix of the tile counts (in place) and the bucket total
-static __global__ void k_colscan(uint32_t *__restrict__ hist, uint32_t ntiles, uint32_t B,
-                          uint32_t *__restrict__ new_cnt) {
-    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    uint32_t run = 0;
-    uint32_t t = 0;
-    for (; t + 4 <= ntiles; t += 4) {
-        uint32_t c[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) c[k] = hist[(size_t)(t + k) * B + b];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            hist[(size_t)(t + k) * B + b] = run;
-            run += c[k];
-        }
-    }
-    for (; t < ntiles; t++) {
-        const size_t k = (size_t)t * B + b;
-        const uint32_t c = hist[k];
-        hist[k] = run;
-        run += c;
-    }
-    new_cnt[b] = run;
-}
-
-// one 1024-thread workgroup: stage_off = excl-scan(new_cnt). Every lane sums its run of `per`
-// consecutive buckets with all loads issued at once (one memory latency for the whole scan), the
-// lane sums are scanned by wave shuffles + one LDS round, and the lane re-reads its run (L2-resident
-// now) to write the offsets.
-constexpr uint32_t PLAN_PER = 32;  // B <= 1024 * PLAN_PER = 2^15 (B is a power of two)
-static __global__ void __launch_bounds__(1024)
-k_plan(const uint32_t *__restrict__ new_cnt, uint32_t B, uint32_t *__restrict__ stage_off) {
-    __shared__ uint64_t w_a[16];
+// per bucket: exclusive prefix of the tile counts (in place), the bucket total, and
+// stage_off = excl-scan(new_cnt) across the whole grid (COLSCAN_T buckets per workgroup).
+// The scan over the workgroups is a look-back: a workgroup publishes the sum of its buckets' totals
+// as one status word (bit 63: published; the sum is below 2^32), then adds up the words of the
+// workgroups before it. Workgroups take their logical index from a ticket, so a workgroup only
+// waits on workgroups that already run, and those publish before they wait on anything.
+// `scan`: [0] the ticket, [1 + w] the status of logical workgroup w, all zero at launch (k_hist).
+constexpr uint32_t COLSCAN_T = 256;
+constexpr unsigned long long COLSCAN_DONE = 1ULL << 63;
+static __global__ void __launch_bounds__(COLSCAN_T)
+k_colscan(uint32_t *__restrict__ hist, uint32_t ntiles, uint32_t B, uint32_t *__restrict__ new_cnt,
+          uint32_t *__restrict__ stage_off, unsigned long long *scan) {
+    __shared__ uint32_t s_wg, s_w[COLSCAN_T / 64];
+    __shared__ unsigned long long s_base;
+    if (threadIdx.x == 0) s_wg = (uint32_t)atomicAdd(&scan[0], 1ULL);
+    __syncthreads();
+    const uint32_t wg = s_wg;
     const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const uint32_t per = B >= 1024 ? B / 1024 : 1u;  // <= PLAN_PER
-    const uint32_t b0 = threadIdx.x * per;
-    const uint32_t cnt = b0 < B ? per : 0u;
-    uint64_t sa = 0;
-    if (per >= 4) {
-        uint4 x[PLAN_PER / 4];
+    const uint32_t b = wg * COLSCAN_T + threadIdx.x;
+    uint32_t run = 0;
+    if (b < B) {
+        uint32_t t = 0;
+        for (; t + 4 <= ntiles; t += 4) {
+            uint32_t c[4];
 #pragma unroll
-        for (uint32_t k = 0; k < PLAN_PER / 4; k++) x[k] = reinterpret_cast<const uint4 *>(new_cnt + b0)[min(k, per / 4 - 1)];
+            for (int k = 0; k < 4; k++) c[k] = hist[(size_t)(t + k) * B + b];
 #pragma unroll
-        for (uint32_t k = 0; k < PLAN_PER / 4; k++)
-            if (4 * k < per) sa += (uint64_t)x[k].x + x[k].y + x[k].z + x[k].w;
-    } else {
-        for (uint32_t k = 0; k < cnt; k++) sa += new_cnt[b0 + k];
+            for (int k = 0; k < 4; k++) {
+                hist[(size_t)(t + k) * B + b] = run;
+                run += c[k];
+            }
+        }
+        for (; t < ntiles; t++) {
+            const size_t k = (size_t)t * B + b;
+            const uint32_t c = hist[k];
+            hist[k] = run;
+            run += c;
+        }
+        new_cnt[b] = run;
     }
-    uint64_t ia = sa;
+    // the workgroup's own buckets: inclusive scan by wave shuffles + one LDS round
+    uint32_t incl = run;
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
-        const uint64_t xa = __shfl_up(ia, d);
-        if (lane >= (uint32_t)d) ia += xa;
+        const uint32_t x = __shfl_up(incl, d);
+        if (lane >= (uint32_t)d) incl += x;
     }
-    if (lane == 63) w_a[w] = ia;
+    if (lane == 63) s_w[w] = incl;
     __syncthreads();
-    uint64_t ra = ia - sa;
-    for (uint32_t ww = 0; ww < w; ww++) ra += w_a[ww];
-    if (per >= 4) {
-#pragma unroll
-        for (uint32_t k = 0; k < PLAN_PER / 4; k++) {
-            if (4 * k >= per) break;
-            const uint4 xk = reinterpret_cast<const uint4 *>(new_cnt + b0)[k];
-            const uint32_t xs[4] = {xk.x, xk.y, xk.z, xk.w};
-            uint32_t so[4];
-#pragma unroll
-            for (int e = 0; e < 4; e++) {
-                so[e] = (uint32_t)ra;
-                ra += xs[e];
-            }
-            reinterpret_cast<uint4 *>(stage_off + b0)[k] = make_uint4(so[0], so[1], so[2], so[3]);
-        }
-    } else {
-        for (uint32_t k = 0; k < cnt; k++) {
-            stage_off[b0 + k] = (uint32_t)ra;
-            ra += new_cnt[b0 + k];
-        }
+    uint32_t before = incl - run, total = 0;
+    for (uint32_t ww = 0; ww < COLSCAN_T / 64; ww++) {
+        if (ww < w) before += s_w[ww];
+        total += s_w[ww];
     }
+    if (threadIdx.x == 0)
+        __hip_atomic_store(&scan[1 + wg], COLSCAN_DONE | total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (w == 0) {  // the earlier workgroups' sums (at most B / COLSCAN_T = 128 words: two per lane)
+        unsigned long long sum = 0;
+        for (uint32_t j = lane; j < wg; j += 64) {
+            unsigned long long st;
+            while (!((st = __hip_atomic_load(&scan[1 + j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) & COLSCAN_DONE))
+                __builtin_amdgcn_s_sleep(1);
+            sum += st & ~COLSCAN_DONE;
+        }
+        for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d);
+        if (lane == 0) s_base = sum;
+    }
+    __syncthreads();
+    if (b < B) stage_off[b] = (uint32_t)s_base + before;
 }
+
+constexpr uint32_t PLAN_PER = 32;  // buckets per thread of a 1024-thread plan workgroup: B <= 2^15
 
 __device__ inline void store_rec(Rec *dst, const Rec &r) {
     const uint4 *s = reinterpret_cast<const uint4 *>(&r);
@@ -2683,15 +2680,6 @@ k_merge_gen_small(MergeArgs a) {
 
 // Validation of a whole batch before a chunked apply commits its first chunk (the checks k_scatter
 // makes per chunk; a batch is applied all or nothing).
-// Rows in the state after an apply: the sum of the regions' entry counts (sizes the regions).
-static __global__ void __launch_bounds__(1024) k_sum_used(const uint32_t *__restrict__ used, uint32_t B,
-                                                          unsigned long long *misc) {
-    unsigned long long t = 0;
-    for (uint32_t b = threadIdx.x; b < B; b += 1024) t += used[b];
-    for (int d = 32; d >= 1; d >>= 1) t += __shfl_xor(t, d);
-    if ((threadIdx.x & 63) == 0 && t) atomicAdd(&misc[MISC_ROWS], t);
-}
-
 static __global__ void k_validate(BatchDev in, uint32_t nsites, const uint16_t *__restrict__ ncols, uint32_t ntables,
                                   unsigned long long *misc) {
     uint32_t err = 0, wide = 0;
@@ -2734,13 +2722,46 @@ static __global__ void k_validate(BatchDev in, uint32_t nsites, const uint16_t *
     if (__any(wide != 0) && (threadIdx.x & 63) == 0) atomicOr(&misc[3], 1ULL);
 }
 
-// crsql_db_versions fold after a batch that passed validation (misc[0]: k_scatter's error bits; a
-// batch that fails them is never merged)
-static __global__ void k_dbv_fold(unsigned long long *__restrict__ dbv, const unsigned long long *__restrict__ batch,
-                           uint32_t nsites, const unsigned long long *__restrict__ misc) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (misc[0]) return;
-    if (i < nsites && batch[i] > dbv[i]) dbv[i] = batch[i];
+// The tail of an apply, one workgroup behind the merge bodies:
+//   - crsql_db_versions fold after a batch that passed validation (misc[0]: k_scatter's error bits; a
+//     batch that fails them is never merged); nsites = 0 skips it (the sum re-run after further rounds);
+//   - rows in the state after the apply: the sum of the regions' entry counts (sizes the regions),
+//     stored to misc[MISC_ROWS];
+//   - the misc words written to `out`, the host's pinned copy (read after the stream is synchronised).
+// Every lane's loads of `used` are issued at once (B <= 2^15: at most 8 x 16 B per lane).
+constexpr uint32_t TAIL_T = 1024;
+static __global__ void __launch_bounds__(TAIL_T)
+k_apply_tail(unsigned long long *__restrict__ dbv, const unsigned long long *__restrict__ batch, uint32_t nsites,
+             const uint32_t *__restrict__ used, uint32_t B, unsigned long long *misc, unsigned long long *out) {
+    __shared__ unsigned long long s_w[TAIL_T / 64];
+    unsigned long long t = 0;
+    if (B >= 4) {
+        const uint32_t n4 = B / 4;  // (B is a power of two)
+        uint4 x[PLAN_PER / 4];
+#pragma unroll
+        for (uint32_t k = 0; k < PLAN_PER / 4; k++)
+            x[k] = reinterpret_cast<const uint4 *>(used)[min(threadIdx.x + k * TAIL_T, n4 - 1)];
+#pragma unroll
+        for (uint32_t k = 0; k < PLAN_PER / 4; k++)
+            if (threadIdx.x + k * TAIL_T < n4) t += (unsigned long long)x[k].x + x[k].y + x[k].z + x[k].w;
+    } else if (threadIdx.x < B) {
+        t = used[threadIdx.x];
+    }
+    for (int d = 32; d >= 1; d >>= 1) t += __shfl_xor(t, d);
+    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = t;
+    if (!misc[0])
+        for (uint32_t i = threadIdx.x; i < nsites; i += TAIL_T)
+            if (batch[i] > dbv[i]) dbv[i] = batch[i];
+    __syncthreads();
+    if (threadIdx.x < (uint32_t)MISC_WORDS) {
+        unsigned long long v = misc[threadIdx.x];
+        if (threadIdx.x == (uint32_t)MISC_ROWS) {
+            v = 0;
+            for (uint32_t ww = 0; ww < TAIL_T / 64; ww++) v += s_w[ww];
+            misc[MISC_ROWS] = v;
+        }
+        out[threadIdx.x] = v;
+    }
 }
 
 // Export / materialisation: every present clock record of the row store, row by row (rows in slot
@@ -2853,6 +2874,37 @@ static __global__ void k_rehash(const RowEnt *__restrict__ old_ent, uint32_t old
         const RowEnt re = old_ent[((size_t)b << old_log2S) + s];
         if (re.tag == 0) continue;
         rs_insert(rs, b, re.pk, re.tag - 1, re.heap, re.bits);
+    }
+}
+
+// An empty row store in one launch: every region entry (hashed slots: the whole table, whatever the
+// regions' fill counts say), the regions' fill and sentinel words, the heap top and, when rows are
+// tracked, the touched-row count. 16-B stores; the grid is sized to the chip, not to the bytes.
+constexpr uint32_t CLEAR_T = 256, CLEAR_GRID = 256;
+template <bool NT>
+static __global__ void __launch_bounds__(CLEAR_T)
+k_store_clear(RowStore rs, uint32_t B, unsigned long long *touch_n) {
+    const uint32_t t = blockIdx.x * CLEAR_T + threadIdx.x, nt = gridDim.x * CLEAR_T;
+    uint4 *ent = reinterpret_cast<uint4 *>(rs.ent);
+    const size_t n16 = ((size_t)B << rs.log2S) * (sizeof(RowEnt) / 16);
+    const uint4 zero = make_uint4(0u, 0u, 0u, 0u);
+#pragma unroll 4
+    for (size_t i = t; i < n16; i += nt) {
+        if (NT) {
+            typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+            const v4u z = {0u, 0u, 0u, 0u};
+            __builtin_nontemporal_store(z, reinterpret_cast<v4u *>(ent + i));
+        } else {
+            ent[i] = zero;
+        }
+    }
+    for (uint32_t b = t; b < B; b += nt) {
+        rs.used[b] = 0;
+        rs.gen[b] = 0;
+    }
+    if (t == 0) {
+        *rs.heap_top = 0;
+        if (touch_n) *touch_n = 0;
     }
 }
 
