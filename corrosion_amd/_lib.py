@@ -41,7 +41,7 @@ EXPORTS = [
     "corro_booked_insert_db_batch", "corro_affinity_of_type", "corro_table_set_affinity", "corro_set_affinity_policy",
     "corro_ctx_metrics", "corro_table_committed", "corro_ctx_track_touched", "corro_state_export_touched",
     "corro_ctx_set_store_limit", "corro_partition_var", "corro_unpack_var",
-    "corro_values_compact", "corro_ctx_set_values_autocompact",
+    "corro_values_compact", "corro_ctx_set_values_autocompact", "corro_encode_changesets",
 ]
 
 CORRO_CS_FULL, CORRO_CS_EMPTY, CORRO_CS_EMPTY_SET = 0, 1, 2
@@ -131,6 +131,18 @@ class Decoded(C.Structure):
                 ("set_end", C.c_void_p), ("cs_dev", C.c_void_p), ("n_dev", C.c_uint64)]
 
 
+class EncodeIn(C.Structure):
+    _fields_ = [("n", C.c_uint64)] + [(k, C.c_void_p) for k in (
+        "site", "version", "last_seq", "ts", "seq_start", "seq_end", "row_off", "row_count")] + [
+        ("rows", Rows), ("nrows", C.c_uint64), ("max_buf_size", C.c_uint32), ("payload", C.c_uint32),
+        ("cluster_id", C.c_uint16)]
+
+
+class Encoded(C.Structure):
+    _fields_ = [("nframes", C.c_uint64), ("nbytes", C.c_uint64)] + [(k, C.c_void_p) for k in (
+        "span_frame_off", "buf", "frame_off", "frame_seq_start", "frame_seq_end", "frame_row_off", "frame_rows")]
+
+
 class ProcessOut(C.Structure):
     _fields_ = [("known", C.c_void_p), ("impactful", C.c_void_p), ("n_ready", C.c_uint64)]
 
@@ -208,6 +220,7 @@ def lib():
         "corro_bookie_seq_bookkeeping": (i32, [vp, vp, u64, vp, vp, u64, vp, vp, vp]),
         "corro_site_ids": (i32, [vp, vp, u32, vp]),
         "corro_decode_frames": (i32, [vp, C.c_char_p, u64, i32, i32, C.POINTER(Decoded), i32]),
+        "corro_encode_changesets": (i32, [vp, C.POINTER(EncodeIn), i32, C.POINTER(Encoded), i32]),
         "corro_bookie_buffered_versions": (i32, [vp, vp, u64, u64, vp, u64, vp]),
         "corro_bookie_buffered": (i32, [vp, vp, u64, u64, u64, C.POINTER(Rows), u64, vp]),
         "corro_bookie_buffered_value": (i32, [vp, vp, u64, u64, vp, u64, vp]),

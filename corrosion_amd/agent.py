@@ -185,6 +185,12 @@ class Agent:
         from . import serve
         return serve.handle_needs(self, needs, max_buf_size or serve.MAX_CHANGES_BYTES_PER_MESSAGE)
 
+    def handle_needs_frames(self, needs, max_buf_size=None, payload=0, cluster_id=0):
+        """The same answers as wire frames, chunked and encoded on the device (serve.handle_needs_frames)."""
+        from . import serve
+        return serve.handle_needs_frames(self, needs, max_buf_size or serve.MAX_CHANGES_BYTES_PER_MESSAGE, payload,
+                                         cluster_id)
+
     def process_multiple_changes(self, changes):
         """changes: list of ChangeV1 (or (ChangeV1, source, instant) tuples) in arrival order."""
         changes = [c[0] if isinstance(c, tuple) else c for c in changes]

@@ -727,7 +727,7 @@ void corro_ctx_destroy(corro_ctx *ctx) {
                       &ctx->d_agent_in, &ctx->d_agent_batch, &ctx->d_agent_spans, &ctx->d_agent_imp,
                       &ctx->d_agent_out, &ctx->d_agent_aux, &ctx->d_agent_fetch, &ctx->d_agent_aux2, &ctx->d_touch, &ctx->d_touch_n, &ctx->d_touch_stamp, &ctx->d_touch_tmp,
                       &ctx->d_aff_conv, &ctx->d_aff_vals, &ctx->d_gaps_big, &ctx->d_agent_hdr, &ctx->d_wire_map,
-                      &ctx->d_hdr_stage, &ctx->d_pm_ts};
+                      &ctx->d_hdr_stage, &ctx->d_pm_ts, &ctx->d_wire_enc};
     for (DevBuf *b : bufs) b->release();
     ctx->d_pkdir.release();
     ctx->d_pk_scratch.release();

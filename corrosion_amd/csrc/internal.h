@@ -138,6 +138,10 @@ std::string pack_int_pk(int64_t v);
 int values_compact(corro_ctx *ctx, bool dry_run, uint64_t reserve, uint64_t *live_bytes, uint64_t *arena_before,
                    uint64_t *arena_after);
 
+// Device copies of the schema names (ctx->wire_names, wire_toff ...: once) and of the site hash
+// (wire.hip); the decoder and the encoder (wire_encode.hip) both read them.
+int wire_schema_sync(corro_ctx *ctx);
+
 // the rocPRIM kernels' first-use cost paid once per process and device (prims.hip)
 int prims_warm(corro_ctx *ctx);
 // the agent's pinned host areas for a call of `ncs` changesets (agent_dev.hip), ahead of the first call
@@ -248,6 +252,7 @@ struct corro_ctx {
     corro::DevBuf d_wire_schema;  // wire decode: table / column names
     corro::DevBuf d_wire_sites;   // wire decode: hash of the registered site ids
     corro::DevBuf d_wire_map;     // wire decode: kept-frame index map (cs_dev output)
+    corro::DevBuf d_wire_enc;     // wire encode: sizes, prefix sums, span / frame tables, staged host arrays
     bool wire_schema_ready = false;
     const uint8_t *wire_names = nullptr;
     const uint32_t *wire_toff = nullptr, *wire_tlen = nullptr, *wire_tbase = nullptr, *wire_tn = nullptr,

@@ -636,6 +636,10 @@ int wire_tables(corro_ctx *ctx) {
 }
 
 }  // namespace
+
+// the schema names (and the site hash) on the device, for the encoder (wire_encode.hip)
+int wire_schema_sync(corro_ctx *ctx) { return wire_tables(ctx); }
+
 }  // namespace corro
 
 using namespace corro;

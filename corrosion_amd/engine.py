@@ -711,6 +711,82 @@ class MergeEngine:
         res["rows"] = {k: a[:R] for k, a in rows.items()}
         return res
 
+    # ---- wire encode (the send half of a sync need) ------------------------------------------
+    def encode_changesets(self, spans, rows, max_buf_size=8192, payload=0, cluster_id=0):
+        """Rows -> chunked Changeset::Full messages -> length-delimited frames on the GPU
+        (corro_encode_changesets). spans = {"site": u32[], "version": i64[], "last_seq", "ts",
+        "seq_start", "seq_end", "row_off", "row_count": u64[]}, one entry per ChunkedChanges the
+        reference would build; rows = the crsql_changes fields (extract_changes' "rows"). numpy arrays
+        (host) or CUDA tensors (device: nothing but the two totals leaves the GPU). Returns "buf"
+        (uint8, the frames in span order then chunk order), "frame_off" (nframes + 1),
+        "span_frame_off" (n + 1) and per frame "frame_seq_start", "frame_seq_end", "frame_row_off",
+        "frame_rows", in the same memory, plus "nframes" / "nbytes"."""
+        lib = L.lib()
+        span_fields = (("site", np.uint32), ("version", np.int64), ("last_seq", np.uint64), ("ts", np.uint64),
+                       ("seq_start", np.uint64), ("seq_end", np.uint64), ("row_off", np.uint64),
+                       ("row_count", np.uint64))
+        row_fields = [(k, dt) for k, dt in ROW_FIELDS.items() if k != "ts"]
+        on_dev = _is_torch(spans["site"])
+        n, R = int(spans["site"].shape[0]), int(rows["pk"].shape[0])
+        s = L.EncodeIn()
+        s.n, s.nrows = n, R
+        s.max_buf_size, s.payload, s.cluster_id = int(max_buf_size), int(payload), int(cluster_id)
+        keep = []
+        for src, dst, fields, cnt in ((spans, s, span_fields, n), (rows, s.rows, row_fields, R)):
+            for k, dt in fields:
+                a = src[k]
+                if on_dev:
+                    if not a.is_cuda or not a.is_contiguous() or not _int_dtype_ok(a, dt) or int(a.shape[0]) != cnt:
+                        raise ValueError(f"device field {k} must be a contiguous CUDA integer tensor of "
+                                         f"{cnt} x {np.dtype(dt)} width")
+                    setattr(dst, k, a.data_ptr() if cnt else None)
+                else:
+                    a = np.ascontiguousarray(a, dtype=dt)
+                    if a.shape[0] != cnt:
+                        raise ValueError(f"field {k} must hold {cnt} entries")
+                    keep.append(a)
+                    setattr(dst, k, a.ctypes.data if cnt else None)
+        if on_dev:
+            import torch
+            dev = spans["site"].device
+            tdt = {np.uint64: torch.int64, np.uint32: torch.int32, np.uint8: torch.uint8}
+
+            def alloc(cnt, dt):
+                return torch.empty(max(cnt, 1), dtype=tdt[dt], device=dev)
+
+            def ptr(a):
+                return a.data_ptr()
+            sync = torch.cuda.current_stream().synchronize
+        else:
+            def alloc(cnt, dt):
+                return np.zeros(max(cnt, 1), dt)
+
+            def ptr(a):
+                return a.ctypes.data
+
+            def sync():
+                pass
+        mem = L.CORRO_MEM_DEVICE if on_dev else L.CORRO_MEM_HOST
+        o = L.Encoded()
+        sfo = alloc(n + 1, np.uint64)
+        o.span_frame_off = ptr(sfo)
+        sync()
+        L.check(lib.corro_encode_changesets(self._h, C.byref(s), mem, C.byref(o), 0))
+        F, NB = int(o.nframes), int(o.nbytes)
+        if n == 0:
+            sfo[:1] = 0
+        res = {"buf": alloc(NB, np.uint8), "frame_off": alloc(F + 1, np.uint64),
+               "frame_seq_start": alloc(F, np.uint64), "frame_seq_end": alloc(F, np.uint64),
+               "frame_row_off": alloc(F, np.uint64), "frame_rows": alloc(F, np.uint32)}
+        for k, a in res.items():
+            setattr(o, k, ptr(a))
+        sync()
+        L.check(lib.corro_encode_changesets(self._h, C.byref(s), mem, C.byref(o), 1))
+        res = {k: a[:(NB if k == "buf" else F + 1 if k == "frame_off" else F)] for k, a in res.items()}
+        res["span_frame_off"] = sfo[:n + 1]
+        res["nframes"], res["nbytes"] = F, NB
+        return res
+
     # ---- sync need diff -------------------------------------------------------------------
     def compute_needs(self, entries):
         """Batched compute_available_needs over CSR entries (see corrosion_amd.sync)."""

@@ -343,3 +343,132 @@ def handle_needs(agent, needs, max_buf_size=MAX_CHANGES_BYTES_PER_MESSAGE):
 
 def handle_need(agent, actor_id, need, max_buf_size=MAX_CHANGES_BYTES_PER_MESSAGE):
     return handle_needs(agent, [(actor_id, need)], max_buf_size)[0]
+
+
+# ---- handle_need, rows to frames on the device --------------------------------------------------
+
+def _bookie_messages(agent, actor, need, found, in_state, site_ids, max_buf_size):
+    """What the host bookie adds to one need's answer after the state's versions (the same walk as in
+    handle_needs): buffered versions' chunks, then the Empty ranges. found: the versions a Full need
+    got from the state; in_state: a Partial need's version is in the state."""
+    eng = agent.engine
+    out, empties = [], []
+    if isinstance(need, NeedFull):
+        unprocessed = _subtract([(need.start, need.end)], [(v, v) for v in sorted(found)])
+        gaps = agent.bookie.needed(actor)
+        for s, e in unprocessed:                               # :458-542
+            buffered = _buffered_versions(agent.bookie, actor, s, e)
+            for v in buffered:
+                for (rs, re_), last_seq, ts in _seq_bookkeeping(agent.bookie, actor, v):
+                    rows, m = _buffered_rows(agent.bookie, actor, v, rs, re_)
+                    chg = rows_to_changes(eng, site_ids, rows, 0, m, _buffered_long(agent.bookie, actor, v, rows))
+                    send_change_chunks(out, ChunkedChanges(chg, rs, re_, max_buf_size), actor, v, last_seq, ts)
+            empties += _subtract([(s, e)], gaps + [(v, v) for v in buffered])
+    elif isinstance(need, NeedPartial) and not in_state:       # :598-712
+        v = need.version
+        in_gaps = _in_ranges(agent.bookie.needed(actor), v)
+        buffered = bool(_buffered_versions(agent.bookie, actor, v, v))
+        if not buffered and not in_gaps:
+            empties.append((v, v))
+        if buffered:
+            for qs, qe in need.seqs:
+                for (rs, re_), last_seq, ts in _seq_bookkeeping(agent.bookie, actor, v):
+                    hit = (qs <= rs <= qe) or (rs <= qs and re_ >= qe) or (rs <= qe and re_ >= qe) or (qs <= re_ <= qe)
+                    if not hit:
+                        continue
+                    s, e = max(rs, qs), min(re_, qe)
+                    rows, m = _buffered_rows(agent.bookie, actor, v, s, e)
+                    chg = rows_to_changes(eng, site_ids, rows, 0, m, _buffered_long(agent.bookie, actor, v, rows))
+                    send_change_chunks(out, ChunkedChanges(chg, s, e, max_buf_size), actor, v, last_seq, ts)
+    for s, e in _subtract(empties, []):                        # :715-724
+        out.append(ChangeV1(actor, Empty(versions=(s, e), ts=None)))
+    return out
+
+
+def handle_needs_frames(agent, needs, max_buf_size=MAX_CHANGES_BYTES_PER_MESSAGE, payload=0, cluster_id=0):
+    """handle_needs down to the bytes on the wire: per need, the length-delimited frames the reference
+    would send, in order (equal to wire.frames(handle_needs(...)[i], payload)).
+
+    The state's versions never become Change objects: the extraction runs in device mode, the
+    spans (one per ChunkedChanges of handle_need: a Full need's versions, a Partial need's seq
+    ranges) are gathered from its groups on the device, and corro_encode_changesets chunks and
+    encodes them there; the host reads the group ranges per need, the versions found and the
+    finished bytes. The host bookie's messages (buffered versions, Empty ranges) are a handful per
+    need: they take the host encoder and follow the need's device frames, as handle_needs orders them."""
+    import torch
+
+    from . import wire
+    eng = agent.engine
+    ent_site, ent_s, ent_e, ent_ss, ent_se = [], [], [], [], []
+    plan = []
+    for actor, need in needs:                                  # one extraction entry per crsql_changes query
+        site = agent.site(actor)
+        if isinstance(need, NeedFull):
+            plan.append(("full", len(ent_site), site))
+            ent_site.append(site); ent_s.append(need.start); ent_e.append(need.end)
+            ent_ss.append(SEQ_ALL[0]); ent_se.append(SEQ_ALL[1])
+        elif isinstance(need, NeedPartial):
+            plan.append(("partial", len(ent_site), site))
+            for s, e in [SEQ_ALL] + [tuple(r) for r in need.seqs]:
+                ent_site.append(site); ent_s.append(need.version); ent_e.append(need.version)
+                ent_ss.append(max(0, min(s, 0xFFFFFFFF))); ent_se.append(max(0, min(e, 0xFFFFFFFF)))
+        else:
+            plan.append(("none", -1, site))
+    site_ids = dict(enumerate(eng.site_ids()))
+    dev = torch.device("cuda", eng.device)
+
+    def up(a, dt):
+        a = np.asarray(a, dt)
+        return torch.from_numpy(a.view(np.int64 if a.itemsize == 8 else np.int32)).to(dev)
+
+    # spans: (site, group that gives version / last_seq / ts, group that gives the rows or -1, seq
+    # range or None = 0 ..= last_seq), in need order
+    sp_site, sp_meta, sp_rows, sp_s, sp_e, sp_full = [], [], [], [], [], []
+    span_range, found, in_state = [], [], []
+    if ent_site:
+        res = eng.extract_changes({"site": up(ent_site, np.uint32), "start": up(ent_s, np.uint64),
+                                   "end": up(ent_e, np.uint64), "seq_start": up(ent_ss, np.uint32),
+                                   "seq_end": up(ent_se, np.uint32)})
+        grp_off = res["grp_off"].cpu().numpy()
+        versions = res["version"].cpu().numpy()
+    for (actor, need), (kind, k, site) in zip(needs, plan):
+        first = len(sp_site)
+        fnd, ins = set(), False
+        if kind == "full":
+            for g in range(int(grp_off[k]), int(grp_off[k + 1])):      # db_version DESC (:385-394)
+                fnd.add(int(versions[g]))
+                sp_site.append(site); sp_meta.append(g); sp_rows.append(g)
+                sp_s.append(0); sp_e.append(0); sp_full.append(True)
+        elif kind == "partial" and grp_off[k + 1] > grp_off[k]:       # :554-597
+            ins = True
+            for j, (s, e) in enumerate(need.seqs):
+                g0, g1 = int(grp_off[k + 1 + j]), int(grp_off[k + 2 + j])
+                sp_site.append(site); sp_meta.append(int(grp_off[k])); sp_rows.append(g0 if g1 > g0 else -1)
+                sp_s.append(s); sp_e.append(e); sp_full.append(False)
+        span_range.append((first, len(sp_site)))
+        found.append(fnd)
+        in_state.append(ins)
+    dev_bytes = [b""] * len(needs)
+    if sp_site:
+        meta, rws = up(sp_meta, np.int64), up(sp_rows, np.int64)
+        has_rows, full = rws >= 0, torch.from_numpy(np.asarray(sp_full)).to(dev)
+        rws = rws.clamp(min=0)
+        last = res["last_seq"][meta]
+        spans = {"site": up(sp_site, np.uint32), "version": res["version"][meta].contiguous(), "last_seq": last.contiguous(),
+                 "ts": res["ts"][meta].contiguous(), "seq_start": up(sp_s, np.uint64),
+                 "seq_end": torch.where(full, last, up(sp_e, np.uint64)).contiguous(),
+                 "row_off": res["grp_row_off"][rws].contiguous(),
+                 "row_count": torch.where(has_rows, res["grp_rows"][rws], torch.zeros_like(rws)).contiguous()}
+        enc = eng.encode_changesets(spans, res["rows"], max_buf_size, payload, cluster_id)
+        buf = enc["buf"].cpu().numpy().tobytes()
+        fo, sfo = enc["frame_off"].cpu().numpy(), enc["span_frame_off"].cpu().numpy()
+        dev_bytes = [buf[int(fo[int(sfo[a])]):int(fo[int(sfo[b])])] for a, b in span_range]
+    out_all = []
+    for i, (actor, need) in enumerate(needs):
+        msgs = _bookie_messages(agent, actor, need, found[i], in_state[i], site_ids, max_buf_size)
+        if payload == wire.PAYLOAD_SYNC:
+            tail = wire.frames(msgs, wire.PAYLOAD_SYNC)
+        else:
+            tail = b"".join(wire.frame(wire.encode_uni_change(cv, cluster_id)) for cv in msgs)
+        out_all.append(dev_bytes[i] + tail)
+    return out_all

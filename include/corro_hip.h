@@ -682,6 +682,61 @@ typedef struct {
 int corro_decode_frames(corro_ctx *ctx, const uint8_t *buf, uint64_t len, int payload, int mem, corro_decoded *out,
                         int pass);
 
+/* ------------------------------------------------------------------ wire encode */
+
+/* The send half: crsql_changes rows (corro_extract_changes' output, where it lies) -> the chunked
+ * Changeset::Full messages handle_need sends (peer/mod.rs:371-789) -> length-delimited frames, the
+ * layout corro_decode_frames reads. One span = one ChunkedChanges (change.rs:66-178) the reference
+ * would build: the rows of one version (a Full need: seq_start = 0, seq_end = last_seq) or of one
+ * requested seq range of it (a Partial need), in send order (seq ascending). Per span, as
+ * ChunkedChanges + send_change_chunks do:
+ *   - a row's estimated size is Change::estimated_byte_size (change.rs:34-49): len(table) + len(packed
+ *     pk) + len(cid) + value size (NULL 2, INTEGER / REAL 9, TEXT / BLOB 5 + len) + 56;
+ *   - a chunk closes when its running estimate reaches max_buf_size and another row follows: it covers
+ *     (chunk start, the closing row's seq) and the next chunk starts one seq later;
+ *   - a row whose seq equals seq_end ends the span (later rows of the span are not sent);
+ *   - the final chunk ends at seq_end, even with no rows; a span's only chunk is dropped when it is
+ *     empty, starts at 0 and ends at the version's last_seq (peer/mod.rs:746-748).
+ * Each chunk is one frame: u32 big-endian length, the message tags of `payload`, ChangeV1.actor_id =
+ * the 16 bytes of the span's site, Changeset::Full { version, changes, seqs, last_seq, ts } (and the
+ * cluster id for CORRO_PAYLOAD_UNI). Per change: table / column names from the schema by table_cid
+ * (cid 0 = "-1"); pk = pack_columns([Integer(pk)]), or for an interned table the key's canonical
+ * bytes; the value from val_type / val_len / val0 / val1 (a long value's bytes from the value arena
+ * behind its val1 handle); site_id = the 16 bytes of the row's site ordinal. rows.ts is not read.
+ *
+ * Two passes: pass 0 sets nframes / nbytes and fills span_frame_off; the caller allocates; pass 1
+ * fills the rest. `mem` covers every array of both structs; with CORRO_MEM_DEVICE no row byte and no
+ * frame byte crosses PCIe (the totals come back). Every row of `rows` and every span is validated
+ * before any read that depends on it: a table index or cid outside the schema, an unregistered site
+ * ordinal, a value handle outside the arena, an interned key not below its table's count or a span
+ * whose rows lie outside nrows returns CORRO_E_INVALID; a frame payload of 2^32 bytes or more returns
+ * CORRO_E_RANGE. Nothing is written to the pass-1 outputs then. The state is not modified. */
+typedef struct {
+    uint64_t n;                            /* spans */
+    const uint32_t *site;                  /* the actor's site ordinal */
+    const int64_t *version;                /* Changeset::Full.version */
+    const uint64_t *last_seq, *ts;         /* Changeset::Full.last_seq / ts of the version */
+    const uint64_t *seq_start, *seq_end;   /* ChunkedChanges' start_seq and last_seq (the span's end) */
+    const uint64_t *row_off, *row_count;   /* the span's rows in `rows` */
+    corro_rows rows;
+    uint64_t nrows;
+    uint32_t max_buf_size;                 /* MAX_CHANGES_BYTES_PER_MESSAGE = 8192 in the reference */
+    uint32_t payload;                      /* CORRO_PAYLOAD_SYNC / CORRO_PAYLOAD_UNI */
+    uint16_t cluster_id;                   /* CORRO_PAYLOAD_UNI only */
+} corro_encode_in;
+
+typedef struct {
+    uint64_t nframes, nbytes;              /* pass 0 outputs, pass 1 inputs */
+    uint64_t *span_frame_off;              /* n + 1 (pass 0): frames of span i = [off[i], off[i + 1]) */
+    uint8_t *buf;                          /* nbytes: the frames, in span order then chunk order */
+    uint64_t *frame_off;                   /* nframes + 1: byte offset of each frame's length prefix */
+    uint64_t *frame_seq_start, *frame_seq_end;   /* nframes: Changeset::Full.seqs */
+    uint64_t *frame_row_off;               /* nframes: the frame's rows = rows[off, off + frame_rows) */
+    uint32_t *frame_rows;
+} corro_encoded;
+
+int corro_encode_changesets(corro_ctx *ctx, const corro_encode_in *in, int mem, corro_encoded *out, int pass);
+
 #ifdef __cplusplus
 }
 #endif
