@@ -42,6 +42,7 @@ EXPORTS = [
     "corro_ctx_metrics", "corro_table_committed", "corro_ctx_track_touched", "corro_state_export_touched",
     "corro_ctx_set_store_limit", "corro_partition_var", "corro_unpack_var",
     "corro_values_compact", "corro_ctx_set_values_autocompact", "corro_encode_changesets",
+    "corro_plan_requests",
 ]
 
 CORRO_CS_FULL, CORRO_CS_EMPTY, CORRO_CS_EMPTY_SET = 0, 1, 2
@@ -143,6 +144,18 @@ class Encoded(C.Structure):
         "span_frame_off", "buf", "frame_off", "frame_seq_start", "frame_seq_end", "frame_row_off", "frame_rows")]
 
 
+class RequestIn(C.Structure):
+    _fields_ = [("n", C.c_uint64)] + [(k, C.c_void_p) for k in (
+        "site", "need_off", "kind", "start", "end", "sr_off", "sr_n", "s_start", "s_end")] + [
+        ("nneeds", C.c_uint64), ("nseqs", C.c_uint64), ("ngroups", C.c_uint64), ("grp_ent_off", C.c_void_p),
+        ("grp_session", C.c_void_p), ("chunk_size", C.c_uint64), ("drain", C.c_uint32)]
+
+
+class Requests(C.Structure):
+    _fields_ = [("nframes", C.c_uint64), ("nbytes", C.c_uint64)] + [(k, C.c_void_p) for k in (
+        "grp_frame_off", "buf", "frame_off", "frame_entry", "frame_round", "frame_needs")]
+
+
 class ProcessOut(C.Structure):
     _fields_ = [("known", C.c_void_p), ("impactful", C.c_void_p), ("n_ready", C.c_uint64)]
 
@@ -221,6 +234,7 @@ def lib():
         "corro_site_ids": (i32, [vp, vp, u32, vp]),
         "corro_decode_frames": (i32, [vp, C.c_char_p, u64, i32, i32, C.POINTER(Decoded), i32]),
         "corro_encode_changesets": (i32, [vp, C.POINTER(EncodeIn), i32, C.POINTER(Encoded), i32]),
+        "corro_plan_requests": (i32, [vp, C.POINTER(RequestIn), i32, C.POINTER(Requests), i32]),
         "corro_bookie_buffered_versions": (i32, [vp, vp, u64, u64, vp, u64, vp]),
         "corro_bookie_buffered": (i32, [vp, vp, u64, u64, u64, C.POINTER(Rows), u64, vp]),
         "corro_bookie_buffered_value": (i32, [vp, vp, u64, u64, vp, u64, vp]),

@@ -729,6 +729,7 @@ void corro_ctx_destroy(corro_ctx *ctx) {
                       &ctx->d_aff_conv, &ctx->d_aff_vals, &ctx->d_gaps_big, &ctx->d_agent_hdr, &ctx->d_wire_map,
                       &ctx->d_hdr_stage, &ctx->d_pm_ts, &ctx->d_wire_enc};
     for (DevBuf *b : bufs) b->release();
+    for (DevBuf &b : ctx->d_req) b.release();
     ctx->d_pkdir.release();
     ctx->d_pk_scratch.release();
     ctx->d_pk_bad.release();

@@ -253,6 +253,10 @@ struct corro_ctx {
     corro::DevBuf d_wire_sites;   // wire decode: hash of the registered site ids
     corro::DevBuf d_wire_map;     // wire decode: kept-frame index map (cs_dev output)
     corro::DevBuf d_wire_enc;     // wire encode: sizes, prefix sums, span / frame tables, staged host arrays
+    // request planning (req_plan.hip), one buffer per level since each level's size is known only once
+    // the one before it has run: inputs + needs + groups, items, ranges + endpoints, segments,
+    // elements, pieces, staged host outputs
+    corro::DevBuf d_req[7];
     bool wire_schema_ready = false;
     const uint8_t *wire_names = nullptr;
     const uint32_t *wire_toff = nullptr, *wire_tlen = nullptr, *wire_tbase = nullptr, *wire_tn = nullptr,

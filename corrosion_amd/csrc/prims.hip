@@ -31,6 +31,15 @@ int ovf_sort_pairs(void *temp, size_t *temp_bytes, const uint64_t *ki, uint64_t 
     return CORRO_OK;
 }
 
+// keys u64 alone, bits [0, end_bit) (request planning's (segment, order) elements); temp == nullptr ->
+// *temp_bytes = size needed
+int prim_sort_keys_u64(void *temp, size_t *temp_bytes, const uint64_t *ki, uint64_t *ko, uint32_t n, uint32_t end_bit,
+                       hipStream_t s) {
+    const hipError_t e = rocprim::radix_sort_keys(temp, *temp_bytes, ki, ko, n, 0u, end_bit, s);
+    if (e != hipSuccess) return fail(CORRO_E_DEVICE, std::string("radix sort: ") + hipGetErrorString(e));
+    return CORRO_OK;
+}
+
 // inclusive max-scan of u64 values segmented by equal consecutive u32 keys (the agent's per-actor
 // running max of version ends); temp == nullptr -> *temp_bytes = size needed
 int prim_segmax_scan_u64(void *temp, size_t *temp_bytes, const uint32_t *keys, const uint64_t *in, uint64_t *out,

@@ -302,6 +302,122 @@ def decode(res, index, npairs):
     return out
 
 
+_REQ_IN = ("site", "need_off", "kind", "start", "end", "sr_off", "sr_n", "s_start", "s_end", "grp_ent_off",
+           "grp_session")
+_REQ_OUT = (("buf", "uint8", "nbytes", 0), ("frame_off", "int64", "nframes", 1), ("frame_entry", "int64", "nframes", 0),
+            ("frame_round", "int32", "nframes", 0), ("frame_needs", "int32", "nframes", 0))
+
+
+def requests_csr(sessions, site_of):
+    """Flatten sessions (each a list, in server order, of {actor: [Full | Partial, ...]}) into the
+    host arrays of corro_request_in. Servers with an empty map are skipped (peer/mod.rs:1135-1138).
+    Returns (arrays, groups) with groups[g] = (session number, server number)."""
+    A = {k: [] for k in ("site", "kind", "start", "end", "sr_off", "sr_n", "s_start", "s_end", "grp_session")}
+    need_off, grp_ent_off, groups = [0], [0], []
+    for sn, servers in enumerate(sessions):
+        for sv, needs in enumerate(servers):
+            if not needs:
+                continue
+            groups.append((sn, sv))
+            A["grp_session"].append(sn)
+            for actor, lst in needs.items():
+                A["site"].append(site_of(actor))
+                for nd in lst:
+                    part = isinstance(nd, Partial)
+                    A["kind"].append(1 if part else 0)
+                    A["start"].append(nd.version if part else nd.start)
+                    A["end"].append(nd.version if part else nd.end)
+                    A["sr_off"].append(len(A["s_start"]))
+                    A["sr_n"].append(len(nd.seqs) if part else 0)
+                    for s, e in (nd.seqs if part else ()):
+                        A["s_start"].append(s)
+                        A["s_end"].append(e)
+                need_off.append(len(A["kind"]))
+            grp_ent_off.append(len(A["site"]))
+    out = {k: np.array(v, dtype=np.uint32 if k == "site" else np.uint8 if k == "kind" else np.uint64) for k, v in A.items()}
+    out["need_off"] = np.array(need_off, np.uint64)
+    out["grp_ent_off"] = np.array(grp_ent_off, np.uint64)
+    return out, groups
+
+
+def _plan_requests(engine, arr, chunk, drain, device):
+    """corro_plan_requests, both passes, on host numpy arrays or (device=True) CUDA tensors keyed like
+    corro_request_in. Returns nframes, nbytes, grp_frame_off, buf, frame_off, frame_entry, frame_round,
+    frame_needs in the same kind of memory; with device arrays only the two totals reach the host."""
+    lib = L.lib()
+    if device:
+        import torch
+        dev = arr["need_off"].device
+        count = lambda a: int(a.numel())
+        ptr = lambda a: a.data_ptr() if a.numel() else None
+        new = lambda m, dt: torch.empty(max(m, 1), dtype=getattr(torch, dt), device=dev)
+    else:
+        count = lambda a: int(a.size)
+        ptr = lambda a: a.ctypes.data if a.size else None
+        new = lambda m, dt: np.zeros(max(m, 1), dtype=dt)
+        want = {"site": np.uint32, "kind": np.uint8}
+        arr = {k: np.ascontiguousarray(arr[k], dtype=want.get(k, np.uint64)) for k in _REQ_IN}
+    r = L.RequestIn()
+    r.n = count(arr["site"])
+    r.nneeds, r.nseqs, r.ngroups = count(arr["kind"]), count(arr["s_start"]), count(arr["grp_session"])
+    r.chunk_size, r.drain = chunk, drain
+    for k in _REQ_IN:
+        setattr(r, k, ptr(arr[k]))
+    mem = L.CORRO_MEM_DEVICE if device else L.CORRO_MEM_HOST
+    o = L.Requests()
+    res = {"grp_frame_off": new(r.ngroups + 1, "int64")}
+    o.grp_frame_off = ptr(res["grp_frame_off"])
+    if device:
+        torch.cuda.current_stream().synchronize()
+    L.check(lib.corro_plan_requests(engine._h, C.byref(r), mem, C.byref(o), 0))
+    sizes = {"nframes": o.nframes, "nbytes": o.nbytes}
+    for k, dt, size, extra in _REQ_OUT:
+        res[k] = new(sizes[size] + extra, dt)
+        setattr(o, k, ptr(res[k]))
+    if device:
+        torch.cuda.current_stream().synchronize()
+    L.check(lib.corro_plan_requests(engine._h, C.byref(r), mem, C.byref(o), 1))
+    for k, _dt, size, extra in _REQ_OUT:
+        res[k] = res[k][:sizes[size] + extra]
+    res["grp_frame_off"] = res["grp_frame_off"][:r.ngroups + 1]
+    res.update(sizes)
+    return res
+
+
+def plan_requests_device(engine, needs, site, grp_ent_off, grp_session, chunk=10, drain=10):
+    """Request planning on device-resident needs: `needs` is the CSR dict of _needs_device_1pass (or
+    _needs_device), `site` the int32 site ordinal per entry, grp_ent_off / grp_session int64 group
+    arrays, all CUDA tensors. Returns CUDA tensors (see _plan_requests); no payload touches the host."""
+    arr = {k: needs[k] for k in ("need_off", "kind", "start", "end", "sr_off", "sr_n", "s_start", "s_end")}
+    arr.update(site=site, grp_ent_off=grp_ent_off, grp_session=grp_session)
+    return _plan_requests(engine, arr, chunk, drain, True)
+
+
+def split_requests(res, groups, nsessions, nservers):
+    """Host result of _plan_requests -> per session, per server, the list of (round, frame bytes)."""
+    out = [[[] for _ in range(k)] for k in nservers]
+    assert len(out) == nsessions
+    buf = res["buf"].tobytes()
+    fo, gfo, rnd = res["frame_off"], res["grp_frame_off"], res["frame_round"]
+    for g, (sn, sv) in enumerate(groups):
+        out[sn][sv] = [(int(rnd[f]), buf[int(fo[f]):int(fo[f + 1])]) for f in range(int(gfo[g]), int(gfo[g + 1]))]
+    return out
+
+
+def plan_sync_requests(engine, sessions, chunk=10, drain=10):
+    """parallel_sync's request loop (peer/mod.rs:1131-1318) for many sessions in one call of
+    corro_plan_requests. `sessions` is a list of sessions, each a list in server order of
+    {actor: [Full | Partial, ...]} (compute_available_needs results; actors are 16-byte ids, registered
+    as sites here). Returns, per session and per server, the list of (round, frame bytes) in sending
+    order; a server's frames of one round go out in one write. A server with an empty map gets []."""
+    actors = sorted({a for servers in sessions for needs in servers for a in needs})
+    ords = engine.register_sites(np.frombuffer(b"".join(actors), np.uint8)) if actors else []
+    site = {a: int(o) for a, o in zip(actors, ords)}
+    arr, groups = requests_csr(sessions, site.__getitem__)
+    res = _plan_requests(engine, arr, chunk, drain, False)
+    return split_requests(res, groups, len(sessions), [len(s) for s in sessions])
+
+
 def batch_compute_available_needs(engine, pairs):
     """compute_available_needs for many (ours, theirs) pairs in one kernel launch pair."""
     ent, index = entries_from_states(pairs)

@@ -113,6 +113,68 @@ def encode_uni_change(cv, cluster_id=0):
     return _u32(0) + _u32(0) + _u32(0) + encode_changev1(cv) + struct.pack("<H", cluster_id)
 
 
+def encode_sync_request(actor_id, needs):
+    """SyncMessage::V1(SyncMessageV1::Request(vec![(actor_id, needs)])) (sync.rs:19-30, SyncRequestV1 =
+    Vec<(ActorId, Vec<SyncNeedV1>)>): u32 0, u32 4, u32 1, the 16 id bytes, u32 count, then per need
+    Full = u32 0 + versions start, end; Partial = u32 1 + version + Vec of seq ranges (sync.rs:252-264).
+    `needs` holds sync.Full / sync.Partial; SyncNeedV1::Empty is never requested."""
+    from . import sync as S
+    if len(actor_id) != 16:
+        raise ValueError("an actor id is 16 bytes")
+    out = [_u32(0), _u32(4), _u32(1), bytes(actor_id), _u32(len(needs))]
+    for nd in needs:
+        if isinstance(nd, S.Full):
+            out.append(_u32(0) + _u64(nd.start) + _u64(nd.end))
+        elif isinstance(nd, S.Partial):
+            out.append(_u32(1) + _u64(nd.version) + _u32(len(nd.seqs)) + b"".join(_u64(s) + _u64(e) for s, e in nd.seqs))
+        else:
+            raise TypeError(nd)
+    return b"".join(out)
+
+
+def decode_sync_request(payload):
+    """The inverse of encode_sync_request for a Request of any number of (actor, needs) pairs: a list
+    of (actor_id, [sync.Full | sync.Partial, ...]). Raises ValueError for anything else."""
+    from . import sync as S
+    pos = 0
+
+    def take(fmt, size):
+        nonlocal pos
+        if pos + size > len(payload):
+            raise ValueError("truncated sync request")
+        v = struct.unpack_from(fmt, payload, pos)[0]
+        pos += size
+        return v
+
+    if take("<I", 4) != 0 or take("<I", 4) != 4:
+        raise ValueError("not a SyncMessage::V1 Request")
+    out = []
+    for _ in range(take("<I", 4)):
+        if pos + 16 > len(payload):
+            raise ValueError("truncated sync request")
+        actor = bytes(payload[pos:pos + 16])
+        pos += 16
+        needs = []
+        for _ in range(take("<I", 4)):
+            tag = take("<I", 4)
+            if tag == 0:
+                s = take("<Q", 8)
+                needs.append(S.Full(s, take("<Q", 8)))
+            elif tag == 1:
+                v = take("<Q", 8)
+                seqs = []
+                for _ in range(take("<I", 4)):
+                    s = take("<Q", 8)
+                    seqs.append((s, take("<Q", 8)))
+                needs.append(S.Partial(v, tuple(seqs)))
+            else:
+                raise ValueError(f"SyncNeedV1 variant {tag} is not a request")
+        out.append((actor, needs))
+    if pos != len(payload):
+        raise ValueError("trailing bytes after the sync request")
+    return out
+
+
 def frame(payload):
     """LengthDelimitedCodec frame: u32 big-endian length + payload."""
     return struct.pack(">I", len(payload)) + payload

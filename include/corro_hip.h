@@ -737,6 +737,72 @@ typedef struct {
 
 int corro_encode_changesets(corro_ctx *ctx, const corro_encode_in *in, int mem, corro_encoded *out, int pass);
 
+/* ------------------------------------------------------------------ sync request planning */
+
+/* parallel_sync's request loop (peer/mod.rs:1131-1318, chunk_range :907-915) over the need diff's
+ * output: the needs where corro_compute_needs* left them -> per-server
+ * SyncMessage::V1(SyncMessageV1::Request(vec![(actor, needs)])) frames.
+ *
+ * A session is one parallel_sync call; a group is one (session, server), its entries the (actor,
+ * Vec<SyncNeedV1>) pairs of that server's need map in the order given (the reference iterates a
+ * HashMap there). Per group the needs are flattened in order, every Full{s..=e} cut into the blocks
+ * of chunk_range (starts s, s + chunk, ... <= e, each ending at min(start + chunk, e): chunk + 1 wide,
+ * neighbours sharing one version; s > e gives none), and the n items popped from the back: the item at
+ * position p is j = n - 1 - p, round j / drain, slot j % drain. A session's items are processed in
+ * increasing (round, server rank, slot) and each is reduced by what was processed before it in the
+ * session: a Full by every earlier Full of its actor (what is left goes out as its maximal runs), a
+ * Partial -- its seqs coalesced first, adjacent ranges included -- by the earlier Partials of its
+ * (actor, version). An item with something left is one frame:
+ *   u32 BE length | u32 0 | u32 4 | u32 1 | actor_id[16] | u32 nneeds | needs
+ *   Full = u32 0, u64 start, u64 end      Partial = u32 1, u64 version, u32 nseqs, (u64 s, u64 e)*
+ * A group's frames are concatenated in processing order (j ascending).
+ *
+ * Two passes like corro_encode_changesets: pass 0 sets nframes / nbytes and fills grp_frame_off, the
+ * caller allocates, pass 1 fills the rest. `mem` covers every array of both structs; with
+ * CORRO_MEM_DEVICE only the totals cross PCIe. Everything is validated before any read that depends
+ * on it. CORRO_E_INVALID: a kind other than 0 / 1, an unregistered site ordinal, offsets that are not
+ * monotone or leave their array, a decreasing grp_session, a partial seq range with start > end,
+ * chunk_size or drain of 0. CORRO_E_RANGE: a Full end >= 2^63, a seq end of 2^64 - 1, more than
+ * 2^32 - 1 items, a frame payload >= 2^32, and the call's own limits: < 2^32 - 1 entries and needs,
+ * < 2^31 seq ranges and groups in the input; < 2^31 ranges to plan (one per chunk plus every seq range
+ * of every Partial item, counted once per need that names it); <= 2^32 - 1 range segments. A range's
+ * segments are the stretches between the distinct endpoints of its book that it covers: about three
+ * per chunk, one per seq range when the seq ranges of a (session, actor, version) are disjoint, but up
+ * to m^2 / 2 for m nested or heavily overlapping seq ranges of one such book, so the work is quadratic
+ * in those and valid input of that shape can meet the segment limit. The seq end of 2^64 - 1 is
+ * refused because end + 1 is the range's right coordinate; the reference would accept it, no recorded
+ * seq comes near it. Nothing is written to the pass-1 outputs on any error; the state is never touched
+ * and the context stays usable, a poisoned one included (the call reads the site table, not the state).
+ * Needs outside every entry and entries outside every group are validated and otherwise ignored.
+ * Each pass plans from scratch (nothing is kept between pass 0 and pass 1). */
+typedef struct {
+    uint64_t n;                            /* entries */
+    const uint32_t *site;                  /* n: the actor's site ordinal (its 16 id bytes go on the wire) */
+    const uint64_t *need_off;              /* n + 1; the rest is corro_needs_out's layout */
+    const uint8_t *kind;                   /* nneeds: 0 Full{start..=end}, 1 Partial{version: start} */
+    const uint64_t *start, *end;
+    const uint64_t *sr_off, *sr_n;         /* Partial seq ranges: [sr_off, sr_off + sr_n) */
+    const uint64_t *s_start, *s_end;       /* nseqs */
+    uint64_t nneeds, nseqs;
+    uint64_t ngroups;
+    const uint64_t *grp_ent_off;           /* ngroups + 1: group g's entries = [off[g], off[g + 1]) */
+    const uint64_t *grp_session;           /* ngroups, non-decreasing; server rank = index within the session */
+    uint64_t chunk_size;                   /* 10 in the reference */
+    uint32_t drain;                        /* needs popped per server per round: 10 in the reference */
+} corro_request_in;
+
+typedef struct {
+    uint64_t nframes, nbytes;              /* pass 0 outputs, pass 1 inputs */
+    uint64_t *grp_frame_off;               /* ngroups + 1 (pass 0): frames of group g = [off[g], off[g + 1]) */
+    uint8_t *buf;                          /* nbytes: the frames, in group order then processing order */
+    uint64_t *frame_off;                   /* nframes + 1: byte offset of each frame's length prefix */
+    uint64_t *frame_entry;                 /* nframes: the entry the frame's need came from */
+    uint32_t *frame_round;                 /* nframes: the round it is sent in (one write per server per round) */
+    uint32_t *frame_needs;                 /* nframes: needs in the frame (req_len of corro.sync.client.req.sent) */
+} corro_requests;
+
+int corro_plan_requests(corro_ctx *ctx, const corro_request_in *in, int mem, corro_requests *out, int pass);
+
 #ifdef __cplusplus
 }
 #endif
