@@ -42,7 +42,7 @@ EXPORTS = [
     "corro_ctx_metrics", "corro_table_committed", "corro_ctx_track_touched", "corro_state_export_touched",
     "corro_ctx_set_store_limit", "corro_partition_var", "corro_unpack_var",
     "corro_values_compact", "corro_ctx_set_values_autocompact", "corro_encode_changesets",
-    "corro_plan_requests",
+    "corro_plan_requests", "corro_decode_requests", "corro_need_spans",
 ]
 
 CORRO_CS_FULL, CORRO_CS_EMPTY, CORRO_CS_EMPTY_SET = 0, 1, 2
@@ -156,6 +156,32 @@ class Requests(C.Structure):
         "grp_frame_off", "buf", "frame_off", "frame_entry", "frame_round", "frame_needs")]
 
 
+class ReqDecIn(C.Structure):
+    _fields_ = [("buf", C.c_void_p), ("len", C.c_uint64), ("nframes", C.c_uint64), ("frame_off", C.c_void_p),
+                ("book_nsites", C.c_uint32), ("book_known", C.c_void_p), ("book_max", C.c_void_p),
+                ("gap_off", C.c_void_p), ("gap_start", C.c_void_p), ("gap_end", C.c_void_p),
+                ("book_ngaps", C.c_uint64)]
+
+
+class ReqDecOut(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("npairs", "nneeds", "nseqs", "nents")] + [(k, C.c_void_p) for k in (
+        "frame_status", "frame_pair_off", "pair_actor", "pair_site", "pair_need_off", "kind", "start", "end",
+        "sr_off", "sr_n", "s_start", "s_end", "need_site", "need_keep", "need_ent_off", "ent_site", "ent_start",
+        "ent_end", "ent_seq_start", "ent_seq_end", "ent_need")]
+
+
+class SpansIn(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("nneeds", "nseqs", "nents", "ngroups")] + [(k, C.c_void_p) for k in (
+        "kind", "sr_off", "sr_n", "s_start", "s_end", "need_keep", "need_ent_off", "need_site", "grp_off",
+        "version", "last_seq", "ts", "grp_row_off", "grp_rows")]
+
+
+class SpansOut(C.Structure):
+    _fields_ = [("nspans", C.c_uint64)] + [(k, C.c_void_p) for k in (
+        "need_span_off", "in_state", "site", "version", "last_seq", "ts", "seq_start", "seq_end", "row_off",
+        "row_count")]
+
+
 class ProcessOut(C.Structure):
     _fields_ = [("known", C.c_void_p), ("impactful", C.c_void_p), ("n_ready", C.c_uint64)]
 
@@ -235,6 +261,8 @@ def lib():
         "corro_decode_frames": (i32, [vp, C.c_char_p, u64, i32, i32, C.POINTER(Decoded), i32]),
         "corro_encode_changesets": (i32, [vp, C.POINTER(EncodeIn), i32, C.POINTER(Encoded), i32]),
         "corro_plan_requests": (i32, [vp, C.POINTER(RequestIn), i32, C.POINTER(Requests), i32]),
+        "corro_decode_requests": (i32, [vp, C.POINTER(ReqDecIn), i32, C.POINTER(ReqDecOut), i32]),
+        "corro_need_spans": (i32, [vp, C.POINTER(SpansIn), i32, C.POINTER(SpansOut), i32]),
         "corro_bookie_buffered_versions": (i32, [vp, vp, u64, u64, vp, u64, vp]),
         "corro_bookie_buffered": (i32, [vp, vp, u64, u64, u64, C.POINTER(Rows), u64, vp]),
         "corro_bookie_buffered_value": (i32, [vp, vp, u64, u64, vp, u64, vp]),

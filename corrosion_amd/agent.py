@@ -191,6 +191,13 @@ class Agent:
         return serve.handle_needs_frames(self, needs, max_buf_size or serve.MAX_CHANGES_BYTES_PER_MESSAGE, payload,
                                          cluster_id)
 
+    def handle_request_frames(self, buf, frame_off, max_buf_size=None, payload=0, cluster_id=0):
+        """Answer a peer's SyncMessageV1::Request frames, request bytes to response bytes on the device
+        (serve.handle_request_frames)."""
+        from . import serve
+        return serve.handle_request_frames(self, buf, frame_off, max_buf_size or serve.MAX_CHANGES_BYTES_PER_MESSAGE,
+                                           payload, cluster_id)
+
     def process_multiple_changes(self, changes):
         """changes: list of ChangeV1 (or (ChangeV1, source, instant) tuples) in arrival order."""
         changes = [c[0] if isinstance(c, tuple) else c for c in changes]

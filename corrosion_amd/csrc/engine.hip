@@ -730,6 +730,7 @@ void corro_ctx_destroy(corro_ctx *ctx) {
                       &ctx->d_hdr_stage, &ctx->d_pm_ts, &ctx->d_wire_enc};
     for (DevBuf *b : bufs) b->release();
     for (DevBuf &b : ctx->d_req) b.release();
+    for (DevBuf &b : ctx->d_reqdec) b.release();
     ctx->d_pkdir.release();
     ctx->d_pk_scratch.release();
     ctx->d_pk_bad.release();

@@ -142,6 +142,36 @@ int values_compact(corro_ctx *ctx, bool dry_run, uint64_t reserve, uint64_t *liv
 // (wire.hip); the decoder and the encoder (wire_encode.hip) both read them.
 int wire_schema_sync(corro_ctx *ctx);
 
+// The site hash as kernels read it: open addressing over H = mask + 1 slots (a power of two, at most
+// half full), slot h holding a registered id's two little-endian words and its ordinal, 0xFFFFFFFF in
+// an empty slot. wire.hip builds and owns it (ctx->d_wire_sites); the frame decoder and the request
+// decoder (req_decode.hip) look ids up through it. Lookups never insert.
+struct SiteHash {
+    const uint64_t *lo = nullptr, *hi = nullptr;
+    const uint32_t *ord = nullptr;
+    uint32_t mask = 0;
+};
+// the hash brought up to date with the site table, and its view
+int wire_site_hash(corro_ctx *ctx, SiteHash *out);
+
+__device__ inline uint64_t site_mix(uint64_t x) {
+    x ^= x >> 33; x *= 0xff51afd7ed558ccdULL;
+    x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ULL;
+    x ^= x >> 33; return x;
+}
+
+// ordinal of the site id (lo, hi), 0xFFFFFFFF when it is not registered
+__device__ inline uint32_t site_hash_find(const SiteHash &t, uint64_t lo, uint64_t hi) {
+    if (t.mask == 0) return 0xFFFFFFFFu;
+    uint32_t h = (uint32_t)site_mix(lo ^ (hi * 0x9E3779B97F4A7C15ULL)) & t.mask;
+    while (true) {
+        const uint32_t o = t.ord[h];
+        if (o == 0xFFFFFFFFu) return o;
+        if (t.lo[h] == lo && t.hi[h] == hi) return o;
+        h = (h + 1) & t.mask;
+    }
+}
+
 // the rocPRIM kernels' first-use cost paid once per process and device (prims.hip)
 int prims_warm(corro_ctx *ctx);
 // the agent's pinned host areas for a call of `ncs` changesets (agent_dev.hip), ahead of the first call
@@ -257,6 +287,9 @@ struct corro_ctx {
     // the one before it has run: inputs + needs + groups, items, ranges + endpoints, segments,
     // elements, pieces, staged host outputs
     corro::DevBuf d_req[7];
+    // request decode / need spans (req_decode.hip): [0] staged host inputs, per-frame / per-need counts,
+    // offsets and rocPRIM temp, [1] staged host outputs
+    corro::DevBuf d_reqdec[2];
     bool wire_schema_ready = false;
     const uint8_t *wire_names = nullptr;
     const uint32_t *wire_toff = nullptr, *wire_tlen = nullptr, *wire_tbase = nullptr, *wire_tn = nullptr,

@@ -54,12 +54,6 @@ constexpr uint32_t WIRE_LDS = 16384;      // at most this many frame bytes stage
 constexpr uint32_t WIRE_OFFS = 1024;      // at most this many change offsets kept in LDS
 constexpr int32_t ST_NOT_CHANGESET = 1;   // a frame that is not a changeset message (skipped)
 
-__device__ inline uint64_t wmix(uint64_t x) {
-    x ^= x >> 33; x *= 0xff51afd7ed558ccdULL;
-    x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ULL;
-    x ^= x >> 33; return x;
-}
-
 struct WireDev {
     const uint8_t *buf;
     const uint64_t *foff;     // frame payload offsets
@@ -113,14 +107,7 @@ struct Rd {
 };
 
 __device__ inline uint32_t site_lookup(const WireDev &d, uint64_t lo, uint64_t hi) {
-    if (d.hmask == 0) return 0xFFFFFFFFu;
-    uint32_t h = (uint32_t)wmix(lo ^ (hi * 0x9E3779B97F4A7C15ULL)) & d.hmask;
-    while (true) {
-        const uint32_t o = d.hord[h];
-        if (o == 0xFFFFFFFFu) return o;
-        if (d.hlo[h] == lo && d.hhi[h] == hi) return o;
-        h = (h + 1) & d.hmask;
-    }
+    return site_hash_find(SiteHash{d.hlo, d.hhi, d.hord, d.hmask}, lo, hi);
 }
 
 __device__ inline void note_unknown(const WireDev &d, uint64_t lo, uint64_t hi) {
@@ -639,6 +626,17 @@ int wire_tables(corro_ctx *ctx) {
 
 // the schema names (and the site hash) on the device, for the encoder (wire_encode.hip)
 int wire_schema_sync(corro_ctx *ctx) { return wire_tables(ctx); }
+
+int wire_site_hash(corro_ctx *ctx, SiteHash *out) {
+    if (int rc = wire_tables(ctx)) return rc;
+    const uint8_t *sq = ctx->d_wire_sites.as<uint8_t>();
+    const uint32_t H = ctx->wire_hmask + 1;
+    out->lo = (const uint64_t *)sq;
+    out->hi = (const uint64_t *)(sq + al(H * 8ULL));
+    out->ord = (const uint32_t *)(sq + 2 * al(H * 8ULL));
+    out->mask = ctx->wire_hmask;
+    return CORRO_OK;
+}
 
 }  // namespace corro
 

@@ -787,6 +787,155 @@ class MergeEngine:
         res["nframes"], res["nbytes"] = F, NB
         return res
 
+    # ---- sync request decode (the server's half of plan_requests) ---------------------------
+    def _two_pass_io(self, on_dev, dev):
+        """alloc / ptr / sync for a two-pass call's arrays: numpy (host) or CUDA tensors on dev."""
+        if on_dev:
+            import torch
+            tdt = {np.uint64: torch.int64, np.int64: torch.int64, np.uint32: torch.int32, np.int32: torch.int32,
+                   np.uint8: torch.uint8}
+
+            def alloc(cnt, dt):
+                return torch.empty(max(cnt, 1), dtype=tdt[dt], device=dev)
+
+            def ptr(a):
+                return a.data_ptr()
+            return alloc, ptr, torch.cuda.current_stream().synchronize
+
+        def alloc(cnt, dt):
+            return np.zeros(max(cnt, 1), dt)
+
+        def ptr(a):
+            return a.ctypes.data
+        return alloc, ptr, lambda: None
+
+    @staticmethod
+    def _in_field(a, dt, on_dev, name, cnt=None):
+        """One input array as (kept object, pointer or None): a contiguous CUDA integer tensor of dt's
+        width, or a numpy array converted to dt."""
+        if on_dev:
+            if not _is_torch(a) or not a.is_cuda or not a.is_contiguous() or not _int_dtype_ok(a, dt):
+                raise ValueError(f"device field {name} must be a contiguous CUDA integer tensor of {np.dtype(dt)} width")
+            n = int(a.numel())
+        else:
+            a = np.ascontiguousarray(a, dtype=dt)
+            n = int(a.size)
+        if cnt is not None and n != cnt:
+            raise ValueError(f"field {name} must hold {cnt} entries (got {n})")
+        if n == 0:
+            return a, None
+        return a, (a.data_ptr() if on_dev else a.ctypes.data)
+
+    _REQDEC_OUT = (("pair_actor", np.uint8, "npairs", 16, 0), ("pair_site", np.uint32, "npairs", 1, 0),
+                   ("pair_need_off", np.uint64, "npairs", 1, 1), ("kind", np.uint8, "nneeds", 1, 0),
+                   ("start", np.uint64, "nneeds", 1, 0), ("end", np.uint64, "nneeds", 1, 0),
+                   ("sr_off", np.uint64, "nneeds", 1, 0), ("sr_n", np.uint64, "nneeds", 1, 0),
+                   ("s_start", np.uint64, "nseqs", 1, 0), ("s_end", np.uint64, "nseqs", 1, 0),
+                   ("need_site", np.uint32, "nneeds", 1, 0), ("need_keep", np.uint8, "nneeds", 1, 0),
+                   ("need_ent_off", np.uint64, "nneeds", 1, 1), ("ent_site", np.uint32, "nents", 1, 0),
+                   ("ent_start", np.uint64, "nents", 1, 0), ("ent_end", np.uint64, "nents", 1, 0),
+                   ("ent_seq_start", np.uint32, "nents", 1, 0), ("ent_seq_end", np.uint32, "nents", 1, 0),
+                   ("ent_need", np.uint64, "nents", 1, 0))
+
+    def decode_requests(self, buf, frame_off, book=None):
+        """SyncMessageV1::Request frames -> decoded, screened needs and their extraction entries on the
+        GPU (corro_decode_requests). buf: the frames back to back (bytes / numpy uint8, or a CUDA uint8
+        tensor); frame_off: nframes + 1 byte offsets of the length prefixes, in the same memory -- the
+        "buf" / "frame_off" a peer's plan_requests_device returns. book (optional, same memory):
+        {"known": u8[], "max": i64[] (-1 = None), "gap_off": u64[nsites + 1], "gap_start", "gap_end":
+        u64[]} over site ordinals; None = no screen. Returns "frame_status" (int32), "frame_pair_off",
+        per pair "pair_actor" (16 bytes each), "pair_site", "pair_need_off", per need "kind", "start",
+        "end", "sr_off", "sr_n", "need_site", "need_keep", "need_ent_off", "s_start" / "s_end", the
+        entries "ent_site", "ent_start", "ent_end", "ent_seq_start", "ent_seq_end", "ent_need", and
+        the totals "nframes", "npairs", "nneeds", "nseqs", "nents". With device input only the totals
+        reach the host."""
+        lib = L.lib()
+        on_dev = _is_torch(buf)
+        if not on_dev and not isinstance(buf, np.ndarray):
+            buf = np.frombuffer(bytes(buf), np.uint8)
+        keep = []
+        r = L.ReqDecIn()
+        b, r.buf = self._in_field(buf, np.uint8, on_dev, "buf")
+        fo, r.frame_off = self._in_field(frame_off, np.uint64, on_dev, "frame_off")
+        keep += [b, fo]
+        r.len = int(b.numel() if on_dev else b.size)
+        nfo = int(fo.numel() if on_dev else fo.size)
+        if nfo < 1:
+            raise ValueError("frame_off holds nframes + 1 offsets")
+        F = nfo - 1
+        r.nframes = F
+        if book is not None:
+            S = int(book["known"].numel() if on_dev else np.asarray(book["known"]).size)
+            r.book_nsites = S
+            for k, dst, dt, cnt in (("known", "book_known", np.uint8, S), ("max", "book_max", np.int64, S),
+                                    ("gap_off", "gap_off", np.uint64, S + 1), ("gap_start", "gap_start", np.uint64, None),
+                                    ("gap_end", "gap_end", np.uint64, None)):
+                a, p = self._in_field(book[k], dt, on_dev, "book." + k, cnt)
+                keep.append(a)
+                setattr(r, dst, p)
+            r.book_ngaps = int(keep[-1].numel() if on_dev else keep[-1].size)
+        alloc, ptr, sync = self._two_pass_io(on_dev, buf.device if on_dev else None)
+        mem = L.CORRO_MEM_DEVICE if on_dev else L.CORRO_MEM_HOST
+        o = L.ReqDecOut()
+        st, fpo = alloc(F, np.int32), alloc(F + 1, np.uint64)
+        o.frame_status, o.frame_pair_off = ptr(st), ptr(fpo)
+        sync()
+        L.check(lib.corro_decode_requests(self._h, C.byref(r), mem, C.byref(o), 0))
+        tot = {k: int(getattr(o, k)) for k in ("npairs", "nneeds", "nseqs", "nents")}
+        res = {}
+        for k, dt, size, mul, extra in self._REQDEC_OUT:
+            res[k] = alloc(tot[size] * mul + extra, dt)
+            setattr(o, k, ptr(res[k]))
+        sync()
+        L.check(lib.corro_decode_requests(self._h, C.byref(r), mem, C.byref(o), 1))
+        for k, _dt, size, mul, extra in self._REQDEC_OUT:
+            res[k] = res[k][:tot[size] * mul + extra]
+        res["frame_status"], res["frame_pair_off"] = st[:F], fpo[:F + 1]
+        res.update(tot)
+        res["nframes"] = F
+        return res
+
+    def need_spans(self, dec, ext):
+        """Decoded needs + the extraction of their entries -> corro_encode_in's span arrays on the GPU
+        (corro_need_spans). dec: decode_requests' result; ext: extract_changes' result for dec's ent_*
+        arrays (same memory). Returns the spans dict encode_changesets takes ("site", "version",
+        "last_seq", "ts", "seq_start", "seq_end", "row_off", "row_count") plus "need_span_off"
+        (nneeds + 1), "in_state" (per need: a kept Partial's version is in the state) and "nspans"."""
+        lib = L.lib()
+        on_dev = _is_torch(dec["kind"])
+        T, Q, E = int(dec["nneeds"]), int(dec["nseqs"]), int(dec["nents"])
+        G = int(ext["version"].shape[0])
+        s = L.SpansIn()
+        s.nneeds, s.nseqs, s.nents, s.ngroups = T, Q, E, G
+        keep = []
+        for src, k, dt, cnt in ((dec, "kind", np.uint8, T), (dec, "sr_off", np.uint64, T), (dec, "sr_n", np.uint64, T),
+                                (dec, "s_start", np.uint64, Q), (dec, "s_end", np.uint64, Q),
+                                (dec, "need_keep", np.uint8, T), (dec, "need_ent_off", np.uint64, T + 1),
+                                (dec, "need_site", np.uint32, T), (ext, "grp_off", np.uint64, E + 1),
+                                (ext, "version", np.int64, G), (ext, "last_seq", np.uint64, G), (ext, "ts", np.uint64, G),
+                                (ext, "grp_row_off", np.uint64, G), (ext, "grp_rows", np.uint64, G)):
+            a, p = self._in_field(src[k], dt, on_dev, k, cnt)
+            keep.append(a)
+            setattr(s, k, p)
+        alloc, ptr, sync = self._two_pass_io(on_dev, dec["kind"].device if on_dev else None)
+        mem = L.CORRO_MEM_DEVICE if on_dev else L.CORRO_MEM_HOST
+        o = L.SpansOut()
+        nso, ins = alloc(T + 1, np.uint64), alloc(T, np.uint8)
+        o.need_span_off, o.in_state = ptr(nso), ptr(ins)
+        sync()
+        L.check(lib.corro_need_spans(self._h, C.byref(s), mem, C.byref(o), 0))
+        N = int(o.nspans)
+        res = {}
+        for k, dt in (("site", np.uint32), ("version", np.int64), ("last_seq", np.uint64), ("ts", np.uint64),
+                      ("seq_start", np.uint64), ("seq_end", np.uint64), ("row_off", np.uint64), ("row_count", np.uint64)):
+            res[k] = alloc(N, dt)
+            setattr(o, k, ptr(res[k]))
+        sync()
+        L.check(lib.corro_need_spans(self._h, C.byref(s), mem, C.byref(o), 1))
+        res = {k: a[:N] for k, a in res.items()}
+        res["need_span_off"], res["in_state"], res["nspans"] = nso[:T + 1], ins[:T], N
+        return res
+
     # ---- sync need diff -------------------------------------------------------------------
     def compute_needs(self, entries):
         """Batched compute_available_needs over CSR entries (see corrosion_amd.sync)."""

@@ -385,6 +385,118 @@ def _bookie_messages(agent, actor, need, found, in_state, site_ids, max_buf_size
     return out
 
 
+def device_book(agent, dev):
+    """The bookie as corro_decode_requests screens against it: per registered site ordinal, known (the
+    bookie holds a version of the actor), max (BookedVersions::last, -1 = None) and the needed() gaps
+    as a CSR, CUDA tensors on dev."""
+    import torch
+    ids = agent.engine.site_ids()
+    known, mx, gap_off, gs, ge = [], [], [0], [], []
+    for a in ids:
+        last = agent.bookie.last(a)
+        gaps = agent.bookie.needed(a)
+        known.append(1 if last is not None or gaps else 0)
+        mx.append(-1 if last is None else last)
+        gs += [s for s, _ in gaps]
+        ge += [e for _, e in gaps]
+        gap_off.append(len(gs))
+
+    def up(a, dt):
+        a = np.asarray(a, dt)
+        return torch.from_numpy(a.view(np.int64) if a.itemsize == 8 else a).to(dev)
+    return {"known": up(known, np.uint8), "max": up(mx, np.int64), "gap_off": up(gap_off, np.uint64),
+            "gap_start": up(gs, np.uint64), "gap_end": up(ge, np.uint64)}
+
+
+def handle_request_frames(agent, buf, frame_off, max_buf_size=MAX_CHANGES_BYTES_PER_MESSAGE, payload=0, cluster_id=0,
+                          timings=None):
+    """process_sync + handle_need from the request bytes to the response bytes (peer/mod.rs:791-905,
+    :371-789): `buf` holds SyncMessageV1::Request frames back to back and frame_off their nframes + 1
+    byte offsets (bytes / numpy, or CUDA tensors: what a peer's plan_requests_device returns). Returns
+    (frame_status, answers): the int32 status per frame (corro_decode_requests: 0 ok, 1 not a request,
+    2 holds an Empty need, negative = malformed) and, per frame, the response bytes -- per kept need in
+    wire order, the need's device frames and then the host bookie's messages, as handle_needs_frames
+    orders them; b"" for a frame with another status or with every need screened out.
+
+    The path is decode + screen (corro_decode_requests, against device_book) -> extract_changes in
+    device mode -> need_spans -> encode_changesets. The host reads the totals, frame_status, the kept
+    needs' fields with the versions found and in_state (which _bookie_messages needs) and the finished
+    bytes; no state row becomes a Change. timings (optional dict) receives the seconds per stage."""
+    import time
+
+    import torch
+
+    from . import wire
+    eng = agent.engine
+    dev = torch.device("cuda", eng.device)
+    t0 = time.perf_counter()
+
+    def lap(name):
+        nonlocal t0
+        if timings is not None:
+            torch.cuda.synchronize(dev)
+            t1 = time.perf_counter()
+            timings[name] = timings.get(name, 0.0) + (t1 - t0)
+            t0 = t1
+
+    if not torch.is_tensor(buf):
+        buf = torch.from_numpy(np.frombuffer(bytes(buf), np.uint8).copy()).to(dev)
+    if not torch.is_tensor(frame_off):
+        frame_off = torch.from_numpy(np.ascontiguousarray(frame_off, np.uint64).view(np.int64)).to(dev)
+    book = device_book(agent, dev)
+    lap("book")
+    dec = eng.decode_requests(buf, frame_off, book)
+    lap("decode")
+    status = dec["frame_status"].cpu().numpy()
+    F, T = dec["nframes"], dec["nneeds"]
+    answers = [b""] * F
+    if T == 0 or dec["nents"] == 0:
+        return status, answers
+    ext = eng.extract_changes({"site": dec["ent_site"], "start": dec["ent_start"], "end": dec["ent_end"],
+                               "seq_start": dec["ent_seq_start"], "seq_end": dec["ent_seq_end"]})
+    lap("extract")
+    sp = eng.need_spans(dec, ext)
+    lap("spans")
+    spans = {k: sp[k] for k in ("site", "version", "last_seq", "ts", "seq_start", "seq_end", "row_off", "row_count")}
+    enc = eng.encode_changesets(spans, ext["rows"], max_buf_size, payload, cluster_id)
+    lap("encode")
+    # what the host bookie's walk needs: the kept needs, the versions a Full need found, in_state
+    h = {k: dec[k].cpu().numpy() for k in ("frame_pair_off", "pair_need_off", "pair_actor", "kind", "start", "end",
+                                           "sr_off", "sr_n", "s_start", "s_end", "need_keep", "need_ent_off")}
+    nso, ins = sp["need_span_off"].cpu().numpy(), sp["in_state"].cpu().numpy()
+    grp_off, versions = ext["grp_off"].cpu().numpy(), ext["version"].cpu().numpy()
+    out = enc["buf"].cpu().numpy().tobytes()
+    fo, sfo = enc["frame_off"].cpu().numpy(), enc["span_frame_off"].cpu().numpy()
+    lap("readback")
+    site_ids = dict(enumerate(eng.site_ids()))
+    actors = h["pair_actor"].tobytes()
+    for f in range(F):
+        parts = []
+        for p in range(int(h["frame_pair_off"][f]), int(h["frame_pair_off"][f + 1])):
+            actor = actors[16 * p:16 * p + 16]
+            for t in range(int(h["pair_need_off"][p]), int(h["pair_need_off"][p + 1])):
+                if not h["need_keep"][t]:
+                    continue
+                parts.append(out[int(fo[int(sfo[int(nso[t])])]):int(fo[int(sfo[int(nso[t + 1])])])])
+                k = int(h["need_ent_off"][t])
+                if h["kind"][t] == 0:
+                    need = NeedFull(int(h["start"][t]), int(h["end"][t]))
+                    found = {int(v) for v in versions[int(grp_off[k]):int(grp_off[k + 1])]}
+                else:
+                    q0 = int(h["sr_off"][t])
+                    need = NeedPartial(int(h["start"][t]), tuple((int(h["s_start"][q]), int(h["s_end"][q]))
+                                                                 for q in range(q0, q0 + int(h["sr_n"][t]))))
+                    found = set()
+                msgs = _bookie_messages(agent, actor, need, found, bool(ins[t]), site_ids, max_buf_size)
+                if payload == wire.PAYLOAD_SYNC:
+                    parts.append(wire.frames(msgs, wire.PAYLOAD_SYNC))
+                else:
+                    parts.append(b"".join(wire.frame(wire.encode_uni_change(cv, cluster_id)) for cv in msgs))
+        answers[f] = b"".join(parts)
+    lap("bookie")
+    return status, answers
+
+
 def handle_needs_frames(agent, needs, max_buf_size=MAX_CHANGES_BYTES_PER_MESSAGE, payload=0, cluster_id=0):
     """handle_needs down to the bytes on the wire: per need, the length-delimited frames the reference
     would send, in order (equal to wire.frames(handle_needs(...)[i], payload)).

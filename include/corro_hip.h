@@ -803,6 +803,122 @@ typedef struct {
 
 int corro_plan_requests(corro_ctx *ctx, const corro_request_in *in, int mem, corro_requests *out, int pass);
 
+/* ------------------------------------------------------------------ sync request decode */
+
+/* The server's half of those frames: SyncMessageV1::Request frames where they lie -> the decoded
+ * needs, screened against the bookie as process_sync does (peer/mod.rs:841-875), and the kept needs
+ * as extraction entries in corro_extract_in's layout. `buf` / `frame_off` are corro_requests.buf /
+ * frame_off: frame f is buf[frame_off[f], frame_off[f + 1]), its length prefix included (the caller's
+ * codec knows the boundaries; nothing chases length prefixes on the device).
+ *
+ *   u32 BE length | u32 0 | u32 4 | u32 npairs | (actor_id[16] | u32 nneeds | needs)*
+ *   Full = u32 0, u64 start, u64 end      Partial = u32 1, u64 version, u32 nseqs, (u64 s, u64 e)*
+ *
+ * Any npairs is accepted. frame_status[f]: 0 ok; 1 a well-formed message header (SyncMessage::V1, a
+ * SyncMessageV1 tag below 4) that is not a Request (skipped); 2 the frame holds a SyncNeedV1::Empty
+ * (need tag 2), which the reference's handle_need does nothing for (peer/mod.rs:712): the walk stops
+ * there, nothing of the frame is emitted and the host handles it; CORRO_E_INVALID a frame shorter
+ * than its prefix, a prefix that is not the frame's size - 4, a truncated frame, trailing bytes, a
+ * message tag above 4 or a need tag above 2; CORRO_E_RANGE a Full bound or Partial version of 2^63 or
+ * more. A frame with a status other than 0 emits nothing and affects no other frame; the call returns
+ * 0. Every count on the wire is bounded by the bytes left before it sizes a loop (a pair is at least
+ * 20 bytes, a need 5 -- Empty { ts: None } --, a seq range 16), and no read leaves the frame.
+ *
+ * The call itself fails, before anything is written, with CORRO_E_INVALID for a frame_off that
+ * decreases or passes len (not attributable to one frame), a book given in part, book offsets that
+ * are not monotone or leave book_ngaps, or gaps of one site that are not sorted, disjoint and
+ * non-touching (the canonical needed() set, as in corro_gaps_in); CORRO_E_RANGE for 2^31 frames or
+ * more.
+ *
+ * pair_site comes from the engine's site table; an actor that is not registered gets 0xFFFFFFFF and
+ * is NOT registered (a request cannot grow the site table). need_keep restates process_sync: with B
+ * the book of the pair's site, a need is dropped when the site is unknown or at or past book_nsites,
+ * book_known is 0, it is a Full need every version v of which is in B's gaps or above B's max (an
+ * empty range start > end is dropped: `all` over nothing), or a Partial need whose version is. With
+ * every book pointer NULL nothing is screened: every need of a registered actor is kept (one of an
+ * unregistered actor never is: it has no site to extract by).
+ * The reference groups consecutive requests of one actor within a 10-request chunk before this loop
+ * and runs the jobs buffer_unordered, so only frame order, then wire order, is kept here.
+ *
+ * Outputs, all CSR in frame order then wire order. Per need the fields are corro_needs_out's (a
+ * Partial has start = end = version; sr_off of a Full need is the count of seq ranges before it;
+ * seq bounds are kept as sent). A kept Full need gives one entry with every seq; a kept Partial need
+ * one every-seq entry (is the version in the state?) followed by one entry per seq range, its bounds
+ * clamped to 2^32 - 1. Two passes like corro_plan_requests: pass 0 sets the totals and fills
+ * frame_status / frame_pair_off, the caller allocates, pass 1 decodes again and fills the rest (totals
+ * that differ: CORRO_E_INVALID, nothing written). `mem` covers every array of both structs; with
+ * CORRO_MEM_DEVICE only the totals cross PCIe. The state is not read; a poisoned context is served. */
+typedef struct {
+    const uint8_t *buf;
+    uint64_t len;
+    uint64_t nframes;
+    const uint64_t *frame_off;             /* nframes + 1 */
+    /* optional book, CSR over site ordinals [0, book_nsites); all five NULL / 0 = no screen */
+    uint32_t book_nsites;
+    const uint8_t *book_known;             /* the bookie has this actor */
+    const int64_t *book_max;               /* BookedVersions::last, -1 = None */
+    const uint64_t *gap_off;               /* book_nsites + 1 */
+    const uint64_t *gap_start, *gap_end;   /* book_ngaps: needed(), canonical per site */
+    uint64_t book_ngaps;
+} corro_reqdec_in;
+
+typedef struct {
+    uint64_t npairs, nneeds, nseqs, nents; /* pass 0 outputs, pass 1 inputs */
+    int32_t *frame_status;                 /* nframes (pass 0) */
+    uint64_t *frame_pair_off;              /* nframes + 1 (pass 0) */
+    uint8_t *pair_actor;                   /* 16 * npairs */
+    uint32_t *pair_site;                   /* npairs: site ordinal, 0xFFFFFFFF = not registered */
+    uint64_t *pair_need_off;               /* npairs + 1 */
+    uint8_t *kind;                         /* nneeds: 0 Full{start..=end}, 1 Partial{version: start} */
+    uint64_t *start, *end;
+    uint64_t *sr_off, *sr_n;               /* Partial seq ranges: [sr_off, sr_off + sr_n) */
+    uint64_t *s_start, *s_end;             /* nseqs */
+    uint32_t *need_site;                   /* nneeds: the pair's site */
+    uint8_t *need_keep;                    /* nneeds: 1 = passes the screen */
+    uint64_t *need_ent_off;                /* nneeds + 1: the need's extraction entries */
+    uint32_t *ent_site;                    /* nents: corro_extract_in's arrays */
+    uint64_t *ent_start, *ent_end;
+    uint32_t *ent_seq_start, *ent_seq_end;
+    uint64_t *ent_need;                    /* nents: the need the entry belongs to */
+} corro_reqdec_out;
+
+int corro_decode_requests(corro_ctx *ctx, const corro_reqdec_in *in, int mem, corro_reqdec_out *out, int pass);
+
+/* The decoded needs and the extraction of their entries (corro_extract_changes over ent_*) -> the span
+ * arrays of corro_encode_in, as handle_need walks them: a kept Full need gives one span per group of
+ * its entry, in the extraction's db_version DESC order, seqs 0 ..= last_seq, rows the group's; a kept
+ * Partial need whose every-seq entry found a group (in_state = 1) gives one span per requested seq
+ * range, version / last_seq / ts from that group, seq_start / seq_end as requested, rows from the
+ * range's own entry (row_count 0 and row_off = grp_row_off[0] when it found none); any other need
+ * gives none. Two passes: pass 0 sets nspans and fills need_span_off / in_state, pass 1 fills the span
+ * arrays. Offsets are validated before anything is read through them: CORRO_E_INVALID, nothing
+ * written, for a kind above 1, need_ent_off / grp_off that are not monotone or leave nents / ngroups,
+ * a need whose entry count is not the one its kind, keep flag and sr_n give, or seq ranges outside
+ * nseqs. `mem` covers every array of both structs. */
+typedef struct {
+    uint64_t nneeds, nseqs, nents, ngroups;
+    const uint8_t *kind;                   /* nneeds: corro_reqdec_out's need arrays */
+    const uint64_t *sr_off, *sr_n;
+    const uint64_t *s_start, *s_end;       /* nseqs */
+    const uint8_t *need_keep;
+    const uint64_t *need_ent_off;          /* nneeds + 1 */
+    const uint32_t *need_site;
+    const uint64_t *grp_off;               /* nents + 1: corro_extract_out's group arrays */
+    const int64_t *version;                /* ngroups */
+    const uint64_t *last_seq, *ts, *grp_row_off, *grp_rows;
+} corro_spans_in;
+
+typedef struct {
+    uint64_t nspans;                       /* pass 0 output, pass 1 input */
+    uint64_t *need_span_off;               /* nneeds + 1 (pass 0) */
+    uint8_t *in_state;                     /* nneeds (pass 0): a kept Partial's version has a group */
+    uint32_t *site;                        /* nspans: corro_encode_in's span arrays */
+    int64_t *version;
+    uint64_t *last_seq, *ts, *seq_start, *seq_end, *row_off, *row_count;
+} corro_spans_out;
+
+int corro_need_spans(corro_ctx *ctx, const corro_spans_in *in, int mem, corro_spans_out *out, int pass);
+
 #ifdef __cplusplus
 }
 #endif
