@@ -7,8 +7,9 @@ need diff is Full(1 ..= versions) per actor, plan_sync_requests cuts them into t
 are the one request buffer both paths answer.
 
   device  serve.handle_request_frames: corro_decode_requests (decode + screen + extraction entries),
-          corro_extract_changes, corro_need_spans, corro_encode_changesets, then the host bookie's walk
-          per kept need
+          corro_extract_changes, corro_need_spans, corro_encode_changesets, corro_need_tails (the
+          "tails" stage: the Empty frames that end a need's answer), then the join per frame and the
+          host bookie's walk for the needs that touch a buffered version (none here)
   host    the path as it stood before: wire.decode_sync_request per frame, process_sync's screen in
           Python (bisect over the bookie's gaps), then serve.handle_needs_frames over the kept needs
           (its per-need Python loops around the same extraction and encoder)

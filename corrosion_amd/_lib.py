@@ -43,6 +43,7 @@ EXPORTS = [
     "corro_ctx_set_store_limit", "corro_partition_var", "corro_unpack_var",
     "corro_values_compact", "corro_ctx_set_values_autocompact", "corro_encode_changesets",
     "corro_plan_requests", "corro_decode_requests", "corro_need_spans",
+    "corro_need_tails",
 ]
 
 CORRO_CS_FULL, CORRO_CS_EMPTY, CORRO_CS_EMPTY_SET = 0, 1, 2
@@ -182,6 +183,19 @@ class SpansOut(C.Structure):
         "row_count")]
 
 
+class TailsIn(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("nneeds", "nents", "ngroups")] + [(k, C.c_void_p) for k in (
+        "kind", "start", "end", "need_keep", "need_site", "need_ent_off", "in_state", "grp_off", "version")] + [
+        ("book_nsites", C.c_uint32), ("gap_off", C.c_void_p), ("gap_start", C.c_void_p), ("gap_end", C.c_void_p),
+        ("book_ngaps", C.c_uint64), ("buf_off", C.c_void_p), ("buf_version", C.c_void_p), ("book_nbuf", C.c_uint64),
+        ("payload", C.c_uint32), ("cluster_id", C.c_uint16)]
+
+
+class TailsOut(C.Structure):
+    _fields_ = [("nranges", C.c_uint64), ("nbytes", C.c_uint64)] + [(k, C.c_void_p) for k in (
+        "need_tail_off", "need_host", "range_start", "range_end", "buf", "frame_off")]
+
+
 class ProcessOut(C.Structure):
     _fields_ = [("known", C.c_void_p), ("impactful", C.c_void_p), ("n_ready", C.c_uint64)]
 
@@ -263,6 +277,7 @@ def lib():
         "corro_plan_requests": (i32, [vp, C.POINTER(RequestIn), i32, C.POINTER(Requests), i32]),
         "corro_decode_requests": (i32, [vp, C.POINTER(ReqDecIn), i32, C.POINTER(ReqDecOut), i32]),
         "corro_need_spans": (i32, [vp, C.POINTER(SpansIn), i32, C.POINTER(SpansOut), i32]),
+        "corro_need_tails": (i32, [vp, C.POINTER(TailsIn), i32, C.POINTER(TailsOut), i32]),
         "corro_bookie_buffered_versions": (i32, [vp, vp, u64, u64, vp, u64, vp]),
         "corro_bookie_buffered": (i32, [vp, vp, u64, u64, u64, C.POINTER(Rows), u64, vp]),
         "corro_bookie_buffered_value": (i32, [vp, vp, u64, u64, vp, u64, vp]),

@@ -287,8 +287,9 @@ struct corro_ctx {
     // the one before it has run: inputs + needs + groups, items, ranges + endpoints, segments,
     // elements, pieces, staged host outputs
     corro::DevBuf d_req[7];
-    // request decode / need spans (req_decode.hip): [0] staged host inputs, per-frame / per-need counts,
-    // offsets and rocPRIM temp, [1] staged host outputs
+    // request decode / need spans (req_decode.hip) and need tails (need_tails.hip), one call at a time:
+    // [0] staged host inputs, per-frame / per-need counts, offsets and rocPRIM temp, [1] staged host
+    // outputs (need tails: and the site of every range)
     corro::DevBuf d_reqdec[2];
     bool wire_schema_ready = false;
     const uint8_t *wire_names = nullptr;

@@ -936,6 +936,57 @@ class MergeEngine:
         res["need_span_off"], res["in_state"], res["nspans"] = nso[:T + 1], ins[:T], N
         return res
 
+    def need_tails(self, dec, ext, sp, bufbook, payload=0, cluster_id=0):
+        """The Changeset::Empty frames that end the answers to the decoded needs, on the GPU
+        (corro_need_tails). dec: decode_requests' result; ext: extract_changes' result for dec's ent_*
+        arrays; sp: need_spans' result (its "in_state"); bufbook: {"gap_off", "gap_start", "gap_end"
+        (the needed() gaps, as decode_requests' book has them), "buf_off": u64[nsites + 1], "buf_version":
+        u64[] (the buffered versions per site ordinal, ascending)}, all in the same memory. Returns
+        "nranges", "need_tail_off" (nneeds + 1), "need_host" (per need: 1 = it touches a buffered version
+        and the host answers its tail), "range_start", "range_end", "buf" (one frame per range: 49 bytes
+        for payload 0, 55 for the uni payload 1) and "frame_off"."""
+        lib = L.lib()
+        on_dev = _is_torch(dec["kind"])
+        T, E = int(dec["nneeds"]), int(dec["nents"])
+        G = int(ext["version"].shape[0])
+        S = len(bufbook["gap_off"]) - 1
+        if S < 0:
+            raise ValueError("gap_off holds nsites + 1 offsets")
+        r = L.TailsIn()
+        r.nneeds, r.nents, r.ngroups, r.book_nsites = T, E, G, S
+        r.payload, r.cluster_id = payload, cluster_id
+        keep = []
+        for src, k, dt, cnt in ((dec, "kind", np.uint8, T), (dec, "start", np.uint64, T), (dec, "end", np.uint64, T),
+                                (dec, "need_keep", np.uint8, T), (dec, "need_site", np.uint32, T),
+                                (dec, "need_ent_off", np.uint64, T + 1), (sp, "in_state", np.uint8, T),
+                                (ext, "grp_off", np.uint64, E + 1), (ext, "version", np.int64, G),
+                                (bufbook, "gap_off", np.uint64, S + 1), (bufbook, "gap_start", np.uint64, None),
+                                (bufbook, "gap_end", np.uint64, None), (bufbook, "buf_off", np.uint64, S + 1),
+                                (bufbook, "buf_version", np.uint64, None)):
+            a, p = self._in_field(src[k], dt, on_dev, k, cnt)
+            keep.append(a)
+            setattr(r, k, p)
+        r.book_ngaps, r.book_nbuf = int(keep[-3].shape[0]), int(keep[-1].shape[0])
+        if int(keep[-4].shape[0]) != r.book_ngaps:
+            raise ValueError("gap_start and gap_end must hold the same number of gaps")
+        alloc, ptr, sync = self._two_pass_io(on_dev, dec["kind"].device if on_dev else None)
+        mem = L.CORRO_MEM_DEVICE if on_dev else L.CORRO_MEM_HOST
+        o = L.TailsOut()
+        nto, nh = alloc(T + 1, np.uint64), alloc(T, np.uint8)
+        o.need_tail_off, o.need_host = ptr(nto), ptr(nh)
+        sync()
+        L.check(lib.corro_need_tails(self._h, C.byref(r), mem, C.byref(o), 0))
+        N, NB = int(o.nranges), int(o.nbytes)
+        res = {"range_start": alloc(N, np.uint64), "range_end": alloc(N, np.uint64), "buf": alloc(NB, np.uint8),
+               "frame_off": alloc(N + 1, np.uint64)}
+        for k, a in res.items():
+            setattr(o, k, ptr(a))
+        sync()
+        L.check(lib.corro_need_tails(self._h, C.byref(r), mem, C.byref(o), 1))
+        res = {k: a[:(NB if k == "buf" else N + 1 if k == "frame_off" else N)] for k, a in res.items()}
+        res["need_tail_off"], res["need_host"], res["nranges"] = nto[:T + 1], nh[:T], N
+        return res
+
     # ---- sync need diff -------------------------------------------------------------------
     def compute_needs(self, entries):
         """Batched compute_available_needs over CSR entries (see corrosion_amd.sync)."""

@@ -408,6 +408,21 @@ def device_book(agent, dev):
             "gap_start": up(gs, np.uint64), "gap_end": up(ge, np.uint64)}
 
 
+def device_buffered(agent, dev):
+    """The bookie's buffered (partial) versions as corro_need_tails reads them: per registered site
+    ordinal, the versions that hold buffered rows, ascending, as a CSR ("buf_off", "buf_version"), CUDA
+    tensors on dev."""
+    import torch
+    buf_off, bv = [0], []
+    for a in agent.engine.site_ids():
+        bv += _buffered_versions(agent.bookie, a, 0, 0xFFFFFFFFFFFFFFFF)
+        buf_off.append(len(bv))
+
+    def up(a):
+        return torch.from_numpy(np.asarray(a, np.uint64).view(np.int64)).to(dev)
+    return {"buf_off": up(buf_off), "buf_version": up(bv)}
+
+
 def handle_request_frames(agent, buf, frame_off, max_buf_size=MAX_CHANGES_BYTES_PER_MESSAGE, payload=0, cluster_id=0,
                           timings=None):
     """process_sync + handle_need from the request bytes to the response bytes (peer/mod.rs:791-905,
@@ -419,9 +434,13 @@ def handle_request_frames(agent, buf, frame_off, max_buf_size=MAX_CHANGES_BYTES_
     orders them; b"" for a frame with another status or with every need screened out.
 
     The path is decode + screen (corro_decode_requests, against device_book) -> extract_changes in
-    device mode -> need_spans -> encode_changesets. The host reads the totals, frame_status, the kept
-    needs' fields with the versions found and in_state (which _bookie_messages needs) and the finished
-    bytes; no state row becomes a Change. timings (optional dict) receives the seconds per stage."""
+    device mode -> need_spans -> encode_changesets -> need_tails (the Empty frames that end a need's
+    answer, against device_book's gaps and device_buffered). The host reads the totals, frame_status,
+    the kept needs' offsets and the finished bytes, and joins them per frame; no state row becomes a
+    Change. Only a need that touches a buffered version (need_tails' need_host) still takes the host
+    bookie's walk, _bookie_messages, with its fields, the versions found and in_state. timings (optional
+    dict) receives the seconds per stage ("tails": device_buffered and need_tails; "bookie": the join
+    and what the host bookie still answers)."""
     import time
 
     import torch
@@ -460,6 +479,8 @@ def handle_request_frames(agent, buf, frame_off, max_buf_size=MAX_CHANGES_BYTES_
     spans = {k: sp[k] for k in ("site", "version", "last_seq", "ts", "seq_start", "seq_end", "row_off", "row_count")}
     enc = eng.encode_changesets(spans, ext["rows"], max_buf_size, payload, cluster_id)
     lap("encode")
+    tl = eng.need_tails(dec, ext, sp, {**book, **device_buffered(agent, dev)}, payload, cluster_id)
+    lap("tails")
     # what the host bookie's walk needs: the kept needs, the versions a Full need found, in_state
     h = {k: dec[k].cpu().numpy() for k in ("frame_pair_off", "pair_need_off", "pair_actor", "kind", "start", "end",
                                            "sr_off", "sr_n", "s_start", "s_end", "need_keep", "need_ent_off")}
@@ -467,6 +488,8 @@ def handle_request_frames(agent, buf, frame_off, max_buf_size=MAX_CHANGES_BYTES_
     grp_off, versions = ext["grp_off"].cpu().numpy(), ext["version"].cpu().numpy()
     out = enc["buf"].cpu().numpy().tobytes()
     fo, sfo = enc["frame_off"].cpu().numpy(), enc["span_frame_off"].cpu().numpy()
+    nto, need_host = tl["need_tail_off"].cpu().numpy(), tl["need_host"].cpu().numpy()
+    tail, tfs = tl["buf"].cpu().numpy().tobytes(), 49 if payload == wire.PAYLOAD_SYNC else 55
     lap("readback")
     site_ids = dict(enumerate(eng.site_ids()))
     actors = h["pair_actor"].tobytes()
@@ -478,6 +501,9 @@ def handle_request_frames(agent, buf, frame_off, max_buf_size=MAX_CHANGES_BYTES_
                 if not h["need_keep"][t]:
                     continue
                 parts.append(out[int(fo[int(sfo[int(nso[t])])]):int(fo[int(sfo[int(nso[t + 1])])])])
+                if not need_host[t]:                            # its Empty frames, from the device
+                    parts.append(tail[tfs * int(nto[t]):tfs * int(nto[t + 1])])
+                    continue
                 k = int(h["need_ent_off"][t])
                 if h["kind"][t] == 0:
                     need = NeedFull(int(h["start"][t]), int(h["end"][t]))

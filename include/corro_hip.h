@@ -919,6 +919,74 @@ typedef struct {
 
 int corro_need_spans(corro_ctx *ctx, const corro_spans_in *in, int mem, corro_spans_out *out, int pass);
 
+/* What handle_need sends after the state's versions, for the needs that touch nothing buffered: the
+ * Changeset::Empty { versions, ts: None } frames of the versions this node knows and holds no row of
+ * (peer/mod.rs:458-542, :598-712, :715-724), from the decoded needs, the extraction's groups, in_state
+ * of corro_need_spans and the book. The book is a CSR over site ordinals [0, book_nsites): the
+ * needed() gaps as in corro_reqdec_in, and the buffered (partial) versions of each site, strictly
+ * ascending (corro_bookie_buffered_versions over every version).
+ *
+ * Rules, with F the versions of the groups of a Full need's one entry (the extraction lists them
+ * strictly descending, inside start ..= end), G the gaps and P the buffered versions of its site:
+ *   - a need with need_keep = 0, or whose site is at or past book_nsites or the engine's site table,
+ *     gives nothing; so does a Full need with start > end (the screen keeps none);
+ *   - a kept Full need: if a version of start ..= end that is not in F is in P, need_host = 1 and the
+ *     need gives no range (the host builds the buffered chunks and the Empties together); otherwise
+ *     it gives, ascending, the maximal runs of versions of start ..= end that are in none of F, G and
+ *     P. Versions above the book's max are not special: they are Empty like any other;
+ *   - a kept Partial need with in_state = 0: need_host = 1 and no range when its version is in P;
+ *     nothing when it is in G; otherwise the one range (version, version);
+ *   - a kept Partial need with in_state = 1 gives nothing.
+ * One frame per range, in need order then ascending version:
+ *   u32 BE length | sync: u32 0, u32 1 / uni: u32 0, u32 0, u32 0 | the 16 id bytes of need_site (the
+ *   engine's site table) | u32 0 | u64 start | u64 end | u8 0 | uni: u16 cluster_id
+ * 49 bytes (CORRO_PAYLOAD_SYNC) or 55 (CORRO_PAYLOAD_UNI), so nbytes = nranges * that and
+ * frame_off[i] = i * that.
+ *
+ * Two passes: pass 0 sets nranges / nbytes and fills need_tail_off / need_host, pass 1 walks again
+ * and fills range_start / range_end / buf / frame_off (totals that differ from pass 0's:
+ * CORRO_E_INVALID). Everything is validated before anything is read through an offset, and a failed
+ * call writes nothing: CORRO_E_INVALID for a NULL struct or a missing array, a bad mem, pass or
+ * payload, a kind above 1, need_ent_off / grp_off / gap_off / buf_off that are not monotone or leave
+ * nents / ngroups / book_ngaps / book_nbuf, a kept need whose entry count is not its kind's (a Full
+ * need has one entry, a Partial need at least one), gaps of one site that are not sorted, disjoint
+ * and non-touching, buffered versions of one site that are not strictly ascending, a kept Full need
+ * whose group versions are not strictly descending inside start ..= end, or a book given in part
+ * (gap_off and buf_off go together, with their arrays); CORRO_E_RANGE for 2^32 ranges or more.
+ * `mem` covers every array of both structs. The state is not read; a poisoned context is served. */
+typedef struct {
+    uint64_t nneeds, nents, ngroups;
+    const uint8_t *kind;                   /* nneeds: corro_reqdec_out's need arrays */
+    const uint64_t *start, *end;
+    const uint8_t *need_keep;
+    const uint32_t *need_site;
+    const uint64_t *need_ent_off;          /* nneeds + 1 */
+    const uint8_t *in_state;               /* nneeds: corro_spans_out's */
+    const uint64_t *grp_off;               /* nents + 1: corro_extract_out's group arrays */
+    const int64_t *version;                /* ngroups */
+    /* the book, CSR over site ordinals [0, book_nsites); all NULL / 0 = no site has a book */
+    uint32_t book_nsites;
+    const uint64_t *gap_off;               /* book_nsites + 1 */
+    const uint64_t *gap_start, *gap_end;   /* book_ngaps: needed(), canonical per site */
+    uint64_t book_ngaps;
+    const uint64_t *buf_off;               /* book_nsites + 1 */
+    const uint64_t *buf_version;           /* book_nbuf: buffered versions, strictly ascending per site */
+    uint64_t book_nbuf;
+    uint32_t payload;                      /* CORRO_PAYLOAD_SYNC / CORRO_PAYLOAD_UNI */
+    uint16_t cluster_id;                   /* uni only */
+} corro_tails_in;
+
+typedef struct {
+    uint64_t nranges, nbytes;              /* pass 0 outputs, pass 1 inputs */
+    uint64_t *need_tail_off;               /* nneeds + 1 (pass 0): ranges of need t = [off[t], off[t + 1]) */
+    uint8_t *need_host;                    /* nneeds (pass 0): 1 = the host produces this need's tail */
+    uint64_t *range_start, *range_end;     /* nranges */
+    uint8_t *buf;                          /* nbytes: one frame per range */
+    uint64_t *frame_off;                   /* nranges + 1 */
+} corro_tails_out;
+
+int corro_need_tails(corro_ctx *ctx, const corro_tails_in *in, int mem, corro_tails_out *out, int pass);
+
 #ifdef __cplusplus
 }
 #endif
