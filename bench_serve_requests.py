@@ -9,7 +9,10 @@ are the one request buffer both paths answer.
   device  serve.handle_request_frames: corro_decode_requests (decode + screen + extraction entries),
           corro_extract_changes, corro_need_spans, corro_encode_changesets, corro_need_tails (the
           "tails" stage: the Empty frames that end a need's answer), then the join per frame and the
-          host bookie's walk for the needs that touch a buffered version (none here)
+          host bookie's walk for the needs that touch a buffered version (none here). With
+          --assembled: serve.handle_request_frames_assembled, the same stages and then
+          corro_assemble_answers (the "assemble" stage: every frame's answer in one device buffer),
+          one read-back of that buffer and one slice per frame
   host    the path as it stood before: wire.decode_sync_request per frame, process_sync's screen in
           Python (bisect over the bookie's gaps), then serve.handle_needs_frames over the kept needs
           (its per-need Python loops around the same extraction and encoder)
@@ -38,6 +41,8 @@ def main():
     ap.add_argument("--chunk", type=int, default=10)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--assembled", action="store_true",
+                    help="time serve.handle_request_frames_assembled as the device path")
     args = ap.parse_args()
 
     import numpy as np
@@ -71,7 +76,8 @@ def main():
     doff = torch.from_numpy(off.view(np.int64)).to(dev)
 
     def device_path(timings=None):
-        return serve.handle_request_frames(agent, dbuf, doff, timings=timings)[1]
+        serve_frames = serve.handle_request_frames_assembled if args.assembled else serve.handle_request_frames
+        return serve_frames(agent, dbuf, doff, timings=timings)[1]
 
     def host_path():
         sites = {a: i for i, a in enumerate(agent.engine.site_ids())}
@@ -120,7 +126,8 @@ def main():
     line = {"metric": "serving sync requests: request bytes to response bytes, ms", "value": dev_s * 1e3, "unit": "ms",
             "higher_is_better": False, "steps": args.steps, "warmup": args.warmup, "data": "synthetic",
             "config": {"actors": args.actors, "versions": args.versions, "changes_per_version": args.changes,
-                       "peers": args.peers, "chunk": args.chunk, "request_frames": len(frames), "request_bytes": len(buf),
+                       "peers": args.peers, "chunk": args.chunk, "assembled": args.assembled,
+                       "request_frames": len(frames), "request_bytes": len(buf),
                        "response_bytes": sum(len(b) for b in got)},
             "device_path_ms": dev_s * 1e3, "host_path_ms": host_s * 1e3, "host_over_device": host_s / dev_s,
             "device_stage_ms": {k: v * 1e3 for k, v in split.items()}}

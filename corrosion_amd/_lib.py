@@ -43,7 +43,7 @@ EXPORTS = [
     "corro_ctx_set_store_limit", "corro_partition_var", "corro_unpack_var",
     "corro_values_compact", "corro_ctx_set_values_autocompact", "corro_encode_changesets",
     "corro_plan_requests", "corro_decode_requests", "corro_need_spans",
-    "corro_need_tails",
+    "corro_need_tails", "corro_assemble_answers",
 ]
 
 CORRO_CS_FULL, CORRO_CS_EMPTY, CORRO_CS_EMPTY_SET = 0, 1, 2
@@ -196,6 +196,21 @@ class TailsOut(C.Structure):
         "need_tail_off", "need_host", "range_start", "range_end", "buf", "frame_off")]
 
 
+class AssembleIn(C.Structure):
+    _fields_ = [("nframes", C.c_uint64), ("npairs", C.c_uint64), ("nneeds", C.c_uint64),
+                ("frame_pair_off", C.c_void_p), ("pair_need_off", C.c_void_p), ("need_keep", C.c_void_p),
+                ("nspans", C.c_uint64), ("need_span_off", C.c_void_p), ("enc_nframes", C.c_uint64),
+                ("enc_nbytes", C.c_uint64), ("span_frame_off", C.c_void_p), ("enc_frame_off", C.c_void_p),
+                ("enc_buf", C.c_void_p), ("nranges", C.c_uint64), ("tail_nbytes", C.c_uint64),
+                ("need_tail_off", C.c_void_p), ("need_host", C.c_void_p), ("tail_buf", C.c_void_p),
+                ("payload", C.c_uint32)]
+
+
+class Assembled(C.Structure):
+    _fields_ = [("nbytes", C.c_uint64)] + [(k, C.c_void_p) for k in (
+        "need_ans_off", "frame_ans_off", "frame_host", "buf")]
+
+
 class ProcessOut(C.Structure):
     _fields_ = [("known", C.c_void_p), ("impactful", C.c_void_p), ("n_ready", C.c_uint64)]
 
@@ -278,6 +293,7 @@ def lib():
         "corro_decode_requests": (i32, [vp, C.POINTER(ReqDecIn), i32, C.POINTER(ReqDecOut), i32]),
         "corro_need_spans": (i32, [vp, C.POINTER(SpansIn), i32, C.POINTER(SpansOut), i32]),
         "corro_need_tails": (i32, [vp, C.POINTER(TailsIn), i32, C.POINTER(TailsOut), i32]),
+        "corro_assemble_answers": (i32, [vp, C.POINTER(AssembleIn), i32, C.POINTER(Assembled), i32]),
         "corro_bookie_buffered_versions": (i32, [vp, vp, u64, u64, vp, u64, vp]),
         "corro_bookie_buffered": (i32, [vp, vp, u64, u64, u64, C.POINTER(Rows), u64, vp]),
         "corro_bookie_buffered_value": (i32, [vp, vp, u64, u64, vp, u64, vp]),

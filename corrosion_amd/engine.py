@@ -987,6 +987,52 @@ class MergeEngine:
         res["need_tail_off"], res["need_host"], res["nranges"] = nto[:T + 1], nh[:T], N
         return res
 
+    def assemble_answers(self, dec, sp, enc, tl, payload=0):
+        """The per-frame answers to the decoded request frames in one buffer, on the GPU
+        (corro_assemble_answers): per need, in frame order then wire order, its encoded frames and then
+        its Empty tail frames. dec: decode_requests' result; sp: need_spans' result (its
+        "need_span_off"); enc: encode_changesets' result for sp's spans; tl: need_tails' result, all in
+        the same memory (CUDA tensors on one device, or numpy); payload as given to the encoder and to
+        need_tails. Returns, in that memory, "buf" (uint8), "need_ans_off" (nneeds + 1), "frame_ans_off" (nframes + 1: the answer of frame f
+        is buf[off[f]:off[f + 1]]) and "frame_host" (per frame: 1 = a kept need of it has need_host,
+        and the host splices that need's bookie messages in at need_ans_off[t + 1]), plus "nbytes"."""
+        lib = L.lib()
+        on_dev = _is_torch(dec["frame_pair_off"])
+        F, NP, T = int(dec["nframes"]), int(dec["npairs"]), int(dec["nneeds"])
+        NS, NR = int(sp["nspans"]), int(tl["nranges"])
+        r = L.AssembleIn()
+        r.nframes, r.npairs, r.nneeds, r.nspans, r.nranges, r.payload = F, NP, T, NS, NR, int(payload)
+        r.enc_nframes, r.enc_nbytes = (int(enc["nframes"]), int(enc["nbytes"])) if NS else (0, 0)
+        r.tail_nbytes = int(tl["buf"].shape[0])
+        keep = []
+        fields = [(dec, "frame_pair_off", "frame_pair_off", np.uint64, F + 1),
+                  (dec, "pair_need_off", "pair_need_off", np.uint64, NP + 1), (dec, "need_keep", "need_keep", np.uint8, T),
+                  (sp, "need_span_off", "need_span_off", np.uint64, T + 1),
+                  (tl, "need_tail_off", "need_tail_off", np.uint64, T + 1), (tl, "need_host", "need_host", np.uint8, T),
+                  (tl, "buf", "tail_buf", np.uint8, None)]
+        if NS:
+            fields += [(enc, "span_frame_off", "span_frame_off", np.uint64, NS + 1),
+                       (enc, "frame_off", "enc_frame_off", np.uint64, r.enc_nframes + 1),
+                       (enc, "buf", "enc_buf", np.uint8, r.enc_nbytes)]
+        for src, k, dst, dt, cnt in fields:
+            a, p = self._in_field(src[k], dt, on_dev, k, cnt)
+            keep.append(a)
+            setattr(r, dst, p)
+        alloc, ptr, sync = self._two_pass_io(on_dev, dec["frame_pair_off"].device if on_dev else None)
+        mem = L.CORRO_MEM_DEVICE if on_dev else L.CORRO_MEM_HOST
+        o = L.Assembled()
+        nao, fao, fh = alloc(T + 1, np.uint64), alloc(F + 1, np.uint64), alloc(F, np.uint8)
+        o.need_ans_off, o.frame_ans_off, o.frame_host = ptr(nao), ptr(fao), ptr(fh)
+        sync()
+        L.check(lib.corro_assemble_answers(self._h, C.byref(r), mem, C.byref(o), 0))
+        NB = int(o.nbytes)
+        buf = alloc(NB, np.uint8)
+        o.buf = ptr(buf)
+        sync()
+        L.check(lib.corro_assemble_answers(self._h, C.byref(r), mem, C.byref(o), 1))
+        return {"buf": buf[:NB], "need_ans_off": nao[:T + 1], "frame_ans_off": fao[:F + 1], "frame_host": fh[:F],
+                "nbytes": NB}
+
     # ---- sync need diff -------------------------------------------------------------------
     def compute_needs(self, entries):
         """Batched compute_available_needs over CSR entries (see corrosion_amd.sync)."""

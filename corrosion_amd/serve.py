@@ -523,6 +523,113 @@ def handle_request_frames(agent, buf, frame_off, max_buf_size=MAX_CHANGES_BYTES_
     return status, answers
 
 
+def handle_request_frames_assembled(agent, buf, frame_off, max_buf_size=MAX_CHANGES_BYTES_PER_MESSAGE, payload=0,
+                                    cluster_id=0, timings=None):
+    """handle_request_frames with the per-frame join on the device: the same arguments, the same
+    (frame_status, answers), byte for byte.
+
+    The five stages of handle_request_frames run unchanged; then assemble_answers
+    (corro_assemble_answers) lays every frame's answer out in one buffer. The host reads back
+    frame_status, frame_ans_off, frame_host and that buffer (one copy into a pinned staging tensor), and
+    a frame takes one slice. Only when a frame holds a need that touches a buffered version
+    (frame_host) are the need arrays read back too: that frame's needs are walked, sliced by
+    need_ans_off, and _bookie_messages' frames go in after each host need's encoded piece. timings: the
+    keys of handle_request_frames plus "assemble"; the read-backs count under "readback" and the
+    remaining join under "bookie"."""
+    import time
+
+    import torch
+
+    from . import wire
+    eng = agent.engine
+    dev = torch.device("cuda", eng.device)
+    t0 = time.perf_counter()
+
+    def lap(name):
+        nonlocal t0
+        if timings is not None:
+            torch.cuda.synchronize(dev)
+            t1 = time.perf_counter()
+            timings[name] = timings.get(name, 0.0) + (t1 - t0)
+            t0 = t1
+
+    if not torch.is_tensor(buf):
+        buf = torch.from_numpy(np.frombuffer(bytes(buf), np.uint8).copy()).to(dev)
+    if not torch.is_tensor(frame_off):
+        frame_off = torch.from_numpy(np.ascontiguousarray(frame_off, np.uint64).view(np.int64)).to(dev)
+    book = device_book(agent, dev)
+    lap("book")
+    dec = eng.decode_requests(buf, frame_off, book)
+    lap("decode")
+    status = dec["frame_status"].cpu().numpy()
+    F, T = dec["nframes"], dec["nneeds"]
+    answers = [b""] * F
+    if T == 0 or dec["nents"] == 0:
+        return status, answers
+    ext = eng.extract_changes({"site": dec["ent_site"], "start": dec["ent_start"], "end": dec["ent_end"],
+                               "seq_start": dec["ent_seq_start"], "seq_end": dec["ent_seq_end"]})
+    lap("extract")
+    sp = eng.need_spans(dec, ext)
+    lap("spans")
+    spans = {k: sp[k] for k in ("site", "version", "last_seq", "ts", "seq_start", "seq_end", "row_off", "row_count")}
+    enc = eng.encode_changesets(spans, ext["rows"], max_buf_size, payload, cluster_id)
+    lap("encode")
+    tl = eng.need_tails(dec, ext, sp, {**book, **device_buffered(agent, dev)}, payload, cluster_id)
+    lap("tails")
+    asm = eng.assemble_answers(dec, sp, enc, tl, payload)
+    lap("assemble")
+    fao, fhost = asm["frame_ans_off"].cpu().numpy(), asm["frame_host"].cpu().numpy()
+    pinned = getattr(eng, "_answer_staging", None)             # pinned, kept with the engine and grown
+    if pinned is None or pinned.numel() < asm["nbytes"]:
+        pinned = eng._answer_staging = torch.empty(max(asm["nbytes"], 1), dtype=torch.uint8, pin_memory=True)
+    pinned[:asm["nbytes"]].copy_(asm["buf"])
+    out = memoryview(pinned.numpy())[:asm["nbytes"]]
+    hosted = np.flatnonzero(fhost)
+    if len(hosted):                                            # what the host bookie's walk needs
+        h = {k: dec[k].cpu().numpy() for k in ("frame_pair_off", "pair_need_off", "pair_actor", "kind", "start", "end",
+                                               "sr_off", "sr_n", "s_start", "s_end", "need_keep", "need_ent_off")}
+        ins, need_host = sp["in_state"].cpu().numpy(), tl["need_host"].cpu().numpy()
+        grp_off, versions = ext["grp_off"].cpu().numpy(), ext["version"].cpu().numpy()
+        nao = asm["need_ans_off"].cpu().numpy()
+    lap("readback")
+    for f in np.flatnonzero(fhost == 0):
+        a, b = int(fao[f]), int(fao[f + 1])
+        if b > a:
+            answers[f] = bytes(out[a:b])
+    if len(hosted):
+        site_ids = dict(enumerate(eng.site_ids()))
+        actors = h["pair_actor"].tobytes()
+    for f in hosted:
+        parts = []
+        for p in range(int(h["frame_pair_off"][f]), int(h["frame_pair_off"][f + 1])):
+            actor = actors[16 * p:16 * p + 16]
+            t0n, t1n = int(h["pair_need_off"][p]), int(h["pair_need_off"][p + 1])
+            lo = int(nao[t0n])                                 # the device bytes not yet taken
+            for t in range(t0n, t1n):
+                if not h["need_keep"][t] or not need_host[t]:
+                    continue
+                parts.append(bytes(out[lo:int(nao[t + 1])]))   # up to and with this need's encoded piece
+                lo = int(nao[t + 1])
+                k = int(h["need_ent_off"][t])
+                if h["kind"][t] == 0:
+                    need = NeedFull(int(h["start"][t]), int(h["end"][t]))
+                    found = {int(v) for v in versions[int(grp_off[k]):int(grp_off[k + 1])]}
+                else:
+                    q0 = int(h["sr_off"][t])
+                    need = NeedPartial(int(h["start"][t]), tuple((int(h["s_start"][q]), int(h["s_end"][q]))
+                                                                 for q in range(q0, q0 + int(h["sr_n"][t]))))
+                    found = set()
+                msgs = _bookie_messages(agent, actor, need, found, bool(ins[t]), site_ids, max_buf_size)
+                if payload == wire.PAYLOAD_SYNC:
+                    parts.append(wire.frames(msgs, wire.PAYLOAD_SYNC))
+                else:
+                    parts.append(b"".join(wire.frame(wire.encode_uni_change(cv, cluster_id)) for cv in msgs))
+            parts.append(bytes(out[lo:int(nao[t1n])]))
+        answers[f] = b"".join(parts)
+    lap("bookie")
+    return status, answers
+
+
 def handle_needs_frames(agent, needs, max_buf_size=MAX_CHANGES_BYTES_PER_MESSAGE, payload=0, cluster_id=0):
     """handle_needs down to the bytes on the wire: per need, the length-delimited frames the reference
     would send, in order (equal to wire.frames(handle_needs(...)[i], payload)).

@@ -987,6 +987,59 @@ typedef struct {
 
 int corro_need_tails(corro_ctx *ctx, const corro_tails_in *in, int mem, corro_tails_out *out, int pass);
 
+/* The per-frame answers in one buffer: what serve.handle_request_frames joins on the host, from the
+ * outputs of corro_decode_requests, corro_need_spans, corro_encode_changesets and corro_need_tails.
+ * Needs are in frame order, then wire order (frame_pair_off -> pair_need_off is a CSR), so the buffer
+ * is the concatenation over the needs t = 0 .. nneeds - 1 of two pieces each:
+ *   1. the need's encoded frames, enc_buf[ enc_frame_off[span_frame_off[need_span_off[t]]] ..
+ *      enc_frame_off[span_frame_off[need_span_off[t + 1]]] );
+ *   2. the need's Empty tail frames, tail_buf[ tfs * need_tail_off[t] .. tfs * need_tail_off[t + 1] ),
+ *      tfs = 49 (CORRO_PAYLOAD_SYNC) or 55 (CORRO_PAYLOAD_UNI).
+ * Piece lengths come from the offsets alone: no frame byte is parsed, and a piece may have any length
+ * >= 0. A need with need_keep = 0 has two empty pieces by construction of its inputs, and a need with
+ * need_host = 1 an empty tail (corro_need_tails gives it no range): the host splices its bookie
+ * messages in at need_ans_off[t + 1]. need_ans_off[t] is the offset of need t's first piece,
+ * frame_ans_off[f] = need_ans_off[pair_need_off[frame_pair_off[f]]] (a frame with no pair or no need
+ * has an empty answer), and frame_host[f] = 1 when a need of the frame has need_keep and need_host.
+ *
+ * Two passes: pass 0 sets nbytes and fills need_ans_off / frame_ans_off / frame_host, the caller
+ * allocates buf, pass 1 computes the offsets again and copies (an nbytes that differs from pass 0's:
+ * CORRO_E_INVALID). Everything is validated before anything is read through an offset, and a failed
+ * call writes nothing: CORRO_E_INVALID for a NULL struct or a missing array (with nspans = 0 the
+ * encoder's three arrays are not read and may be NULL, as may enc_buf with enc_nbytes = 0 and tail_buf
+ * with nranges = 0), a bad mem, pass or payload, one of the six offset arrays not monotone or ending
+ * past its bound (frame_pair_off <= npairs, pair_need_off <= nneeds, need_span_off <= nspans,
+ * span_frame_off <= enc_nframes, enc_frame_off <= enc_nbytes, need_tail_off <= nranges), or
+ * tail_nbytes != nranges * tfs; CORRO_E_RANGE for 2^40 or more of a count or 2^32 ranges or more.
+ * `mem` covers every array of both structs. The state is not read; a poisoned context is served. */
+typedef struct {
+    uint64_t nframes, npairs, nneeds;
+    const uint64_t *frame_pair_off;        /* nframes + 1: corro_reqdec_out's */
+    const uint64_t *pair_need_off;         /* npairs + 1 */
+    const uint8_t *need_keep;              /* nneeds */
+    uint64_t nspans;                       /* corro_spans_out's */
+    const uint64_t *need_span_off;         /* nneeds + 1 */
+    uint64_t enc_nframes, enc_nbytes;      /* corro_encoded's nframes / nbytes */
+    const uint64_t *span_frame_off;        /* nspans + 1 */
+    const uint64_t *enc_frame_off;         /* enc_nframes + 1: corro_encoded's frame_off */
+    const uint8_t *enc_buf;                /* enc_nbytes: corro_encoded's buf */
+    uint64_t nranges, tail_nbytes;         /* corro_tails_out's nranges / nbytes */
+    const uint64_t *need_tail_off;         /* nneeds + 1 */
+    const uint8_t *need_host;              /* nneeds */
+    const uint8_t *tail_buf;               /* tail_nbytes: corro_tails_out's buf */
+    uint32_t payload;                      /* CORRO_PAYLOAD_SYNC / CORRO_PAYLOAD_UNI: the tail frame size */
+} corro_assemble_in;
+
+typedef struct {
+    uint64_t nbytes;                       /* pass 0 output, pass 1 input */
+    uint64_t *need_ans_off;                /* nneeds + 1 (pass 0): pieces of need t = [off[t], off[t + 1]) */
+    uint64_t *frame_ans_off;               /* nframes + 1 (pass 0): answer of frame f = buf[off[f], off[f + 1]) */
+    uint8_t *frame_host;                   /* nframes (pass 0): 1 = a kept need of the frame has need_host */
+    uint8_t *buf;                          /* nbytes (pass 1) */
+} corro_assembled;
+
+int corro_assemble_answers(corro_ctx *ctx, const corro_assemble_in *in, int mem, corro_assembled *out, int pass);
+
 #ifdef __cplusplus
 }
 #endif
