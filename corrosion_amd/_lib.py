@@ -44,6 +44,7 @@ EXPORTS = [
     "corro_values_compact", "corro_ctx_set_values_autocompact", "corro_encode_changesets",
     "corro_plan_requests", "corro_decode_requests", "corro_need_spans",
     "corro_need_tails", "corro_assemble_answers",
+    "corro_bookie_buffered_index", "corro_buffered_spans", "corro_assemble_answers_buffered",
 ]
 
 CORRO_CS_FULL, CORRO_CS_EMPTY, CORRO_CS_EMPTY_SET = 0, 1, 2
@@ -211,6 +212,33 @@ class Assembled(C.Structure):
         "need_ans_off", "frame_ans_off", "frame_host", "buf")]
 
 
+class BufferedIndex(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("nver", "nsr", "nseg", "ntail_gap", "nhost_buf")] + [(k, C.c_void_p) for k in (
+        "ver_off", "version", "last_seq", "ts", "on_device", "sr_off", "sr_start", "sr_end", "seg_off", "seg_pool_off",
+        "seg_seq0", "seg_n", "tail_gap_off", "tail_gap_start", "tail_gap_end", "host_buf_off", "host_buf_version")]
+
+
+class BufSpansIn(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("nneeds", "nseqs", "nents", "ngroups")] + [(k, C.c_void_p) for k in (
+        "kind", "start", "end", "sr_off", "sr_n", "s_start", "s_end", "need_keep", "need_site", "need_ent_off",
+        "in_state", "need_host", "grp_off", "version")] + [
+        ("idx_nsites", C.c_uint32), ("idx_nver", C.c_uint64), ("idx_nsr", C.c_uint64), ("idx_nseg", C.c_uint64)] + [
+        (k, C.c_void_p) for k in ("ver_off", "idx_version", "idx_last_seq", "idx_ts", "on_device", "vsr_off", "vsr_start",
+                                  "vsr_end", "seg_off", "seg_pool_off", "seg_seq0", "seg_n")]
+
+
+class BufSpansOut(C.Structure):
+    _fields_ = [("nspans", C.c_uint64), ("nrows", C.c_uint64)] + [(k, C.c_void_p) for k in (
+        "need_bspan_off", "site", "version", "last_seq", "ts", "seq_start", "seq_end", "row_off", "row_count")] + [
+        ("rows", Rows)]
+
+
+class AssembleBufferedIn(C.Structure):
+    _fields_ = [("base", AssembleIn), ("nbspans", C.c_uint64), ("need_bspan_off", C.c_void_p),
+                ("benc_nframes", C.c_uint64), ("benc_nbytes", C.c_uint64), ("bspan_frame_off", C.c_void_p),
+                ("benc_frame_off", C.c_void_p), ("benc_buf", C.c_void_p)]
+
+
 class ProcessOut(C.Structure):
     _fields_ = [("known", C.c_void_p), ("impactful", C.c_void_p), ("n_ready", C.c_uint64)]
 
@@ -294,6 +322,9 @@ def lib():
         "corro_need_spans": (i32, [vp, C.POINTER(SpansIn), i32, C.POINTER(SpansOut), i32]),
         "corro_need_tails": (i32, [vp, C.POINTER(TailsIn), i32, C.POINTER(TailsOut), i32]),
         "corro_assemble_answers": (i32, [vp, C.POINTER(AssembleIn), i32, C.POINTER(Assembled), i32]),
+        "corro_bookie_buffered_index": (i32, [vp, vp, u32, C.POINTER(BufferedIndex), i32]),
+        "corro_buffered_spans": (i32, [vp, vp, C.POINTER(BufSpansIn), i32, C.POINTER(BufSpansOut), i32]),
+        "corro_assemble_answers_buffered": (i32, [vp, C.POINTER(AssembleBufferedIn), i32, C.POINTER(Assembled), i32]),
         "corro_bookie_buffered_versions": (i32, [vp, vp, u64, u64, vp, u64, vp]),
         "corro_bookie_buffered": (i32, [vp, vp, u64, u64, u64, C.POINTER(Rows), u64, vp]),
         "corro_bookie_buffered_value": (i32, [vp, vp, u64, u64, vp, u64, vp]),

@@ -198,6 +198,15 @@ class Agent:
         return serve.handle_request_frames(self, buf, frame_off, max_buf_size or serve.MAX_CHANGES_BYTES_PER_MESSAGE,
                                            payload, cluster_id)
 
+    def handle_request_frames_buffered(self, buf, frame_off, max_buf_size=None, payload=0, cluster_id=0, timings=None):
+        """The same answers with the buffered (partial) versions served from the device row pool, where
+        process_frames left them, and the per-frame join on the device
+        (serve.handle_request_frames_buffered)."""
+        from . import serve
+        return serve.handle_request_frames_buffered(self, buf, frame_off,
+                                                    max_buf_size or serve.MAX_CHANGES_BYTES_PER_MESSAGE, payload,
+                                                    cluster_id, timings)
+
     def process_multiple_changes(self, changes):
         """changes: list of ChangeV1 (or (ChangeV1, source, instant) tuples) in arrival order."""
         changes = [c[0] if isinstance(c, tuple) else c for c in changes]

@@ -294,6 +294,8 @@ struct corro_bookie {
     std::vector<uint64_t> scratch_ver;                          // process_multiple_changes scratch
 };
 
+corro::DevBufPool *corro::bookie_pool(corro_bookie *bk) { return bk ? bk->pool : nullptr; }
+
 namespace {
 
 // Bookie::ensure (agent.rs:1546-1598) through the site cache; create = false: nullptr for an actor
@@ -2583,6 +2585,110 @@ int corro_bookie_buffered_versions(corro_bookie *bk, const uint8_t *actor_id, ui
     }
     *count = k;
     return CORRO_OK;
+}
+
+// Every site's buffered versions with their seq bookkeeping and, where the key lives in the device
+// pool alone, its segments -- and the two books corro_need_tails takes when those versions are served
+// from the pool (corro_hip.h). Reads the bookie only: nothing is materialised.
+int corro_bookie_buffered_index(corro_bookie *bk, const uint8_t *actor_ids, uint32_t nsites, corro_buffered_index *o,
+                                int pass) {
+    if (!bk || !o || (nsites && !actor_ids)) return fail(CORRO_E_INVALID, "NULL argument");
+    if (pass != 0 && pass != 1) return fail(CORRO_E_INVALID, "pass must be 0 or 1");
+    try {
+        std::vector<uint64_t> ver_off{0}, version, ts, sr_off{0}, sr_start, sr_end, seg_off{0}, seg_pool_off;
+        std::vector<uint64_t> tg_off{0}, tg_start, tg_end, hb_off{0}, hb_version;
+        std::vector<int64_t> last_seq;
+        std::vector<uint8_t> on_device;
+        std::vector<uint32_t> seg_seq0, seg_n;
+        for (uint32_t s = 0; s < nsites; s++) {
+            const ActorId a = actor_of(actor_ids + 16 * (size_t)s);
+            RangeSet tail;
+            auto bit = bk->actors.find(a);
+            if (bit != bk->actors.end()) tail = bit->second.needed;
+            auto so = bk->site_of.find(a);
+            if (so != bk->site_of.end()) {
+                const uint32_t site = so->second;
+                for (size_t i = bk->buffered.lower({site, 0}); i < bk->buffered.slots(); i++) {
+                    const auto &x = bk->buffered.at(i);
+                    if (x.key.first != site) break;
+                    if (x.dead || x.val.empty()) continue;
+                    const uint64_t v = (uint64_t)x.key.second;
+                    const SeqBook *sb = bk->seqbook.find({site, v});
+                    const bool dev = sb && x.val.rows.empty() && !x.val.segs.empty() && !x.val.segs.any_pending();
+                    version.push_back(v);
+                    last_seq.push_back(sb ? (int64_t)sb->last_seq : -1);
+                    ts.push_back(sb ? sb->ts : 0);
+                    on_device.push_back(dev ? 1 : 0);
+                    if (sb) {
+                        std::vector<Range> rs(sb->ranges.begin(), sb->ranges.end());
+                        std::sort(rs.begin(), rs.end());
+                        for (const Range &r : rs) {
+                            sr_start.push_back(r.first);
+                            sr_end.push_back(r.second);
+                        }
+                    }
+                    sr_off.push_back(sr_start.size());
+                    if (dev) {
+                        for (const PoolSeg &g : x.val.segs) {
+                            seg_pool_off.push_back(g.off);
+                            seg_seq0.push_back(g.seq0);
+                            seg_n.push_back(g.n);
+                        }
+                        tail.insert(v, v);
+                    } else {
+                        hb_version.push_back(v);
+                    }
+                    seg_off.push_back(seg_pool_off.size());
+                }
+            }
+            ver_off.push_back(version.size());
+            for (const auto &r : tail.ranges()) {
+                tg_start.push_back(r.first);
+                tg_end.push_back(r.second);
+            }
+            tg_off.push_back(tg_start.size());
+            hb_off.push_back(hb_version.size());
+        }
+        if (pass == 0) {
+            o->nver = version.size();
+            o->nsr = sr_start.size();
+            o->nseg = seg_pool_off.size();
+            o->ntail_gap = tg_start.size();
+            o->nhost_buf = hb_version.size();
+            return CORRO_OK;
+        }
+        if (o->nver != version.size() || o->nsr != sr_start.size() || o->nseg != seg_pool_off.size() ||
+            o->ntail_gap != tg_start.size() || o->nhost_buf != hb_version.size())
+            return fail(CORRO_E_INVALID, "sizes differ from pass 0");
+        if (!o->ver_off || !o->sr_off || !o->seg_off || !o->tail_gap_off || !o->host_buf_off ||
+            (o->nver && (!o->version || !o->last_seq || !o->ts || !o->on_device)) || (o->nsr && (!o->sr_start || !o->sr_end)) ||
+            (o->nseg && (!o->seg_pool_off || !o->seg_seq0 || !o->seg_n)) ||
+            (o->ntail_gap && (!o->tail_gap_start || !o->tail_gap_end)) || (o->nhost_buf && !o->host_buf_version))
+            return fail(CORRO_E_INVALID, "an output array is NULL");
+        auto put = [](auto *dst, const auto &src) {
+            if (!src.empty()) std::memcpy(dst, src.data(), src.size() * sizeof(src[0]));
+        };
+        put(o->ver_off, ver_off);
+        put(o->version, version);
+        put(o->last_seq, last_seq);
+        put(o->ts, ts);
+        put(o->on_device, on_device);
+        put(o->sr_off, sr_off);
+        put(o->sr_start, sr_start);
+        put(o->sr_end, sr_end);
+        put(o->seg_off, seg_off);
+        put(o->seg_pool_off, seg_pool_off);
+        put(o->seg_seq0, seg_seq0);
+        put(o->seg_n, seg_n);
+        put(o->tail_gap_off, tg_off);
+        put(o->tail_gap_start, tg_start);
+        put(o->tail_gap_end, tg_end);
+        put(o->host_buf_off, hb_off);
+        put(o->host_buf_version, hb_version);
+        return CORRO_OK;
+    } catch (const std::bad_alloc &) {
+        return fail(CORRO_E_NOMEM, "host allocation failed in corro_bookie_buffered_index");
+    }
 }
 
 // __corro_buffered_changes rows of (actor, version) with seq in [seq_start, seq_end], seq

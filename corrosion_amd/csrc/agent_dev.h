@@ -153,6 +153,11 @@ DevBufPool *bufpool_new();
 void bufpool_free(DevBufPool *p);
 bool bufpool_usable(corro_ctx *ctx, const DevBufPool *p);
 uint64_t bufpool_top(const DevBufPool *p);
+// the pool's columns, for readers of its rows on the device (buffered_serve.hip): v->n = the top;
+// false when the pool holds no buffer yet
+bool bufpool_view(const DevBufPool *p, corro_changes *v);
+// a bookie's pool (agent.cpp; null: it has none yet)
+DevBufPool *bookie_pool(corro_bookie *bk);
 // per-table counts of the changes of the spans (src, count)
 int agent_dev_table_counts(corro_ctx *ctx, const corro_changes *dv, const std::vector<AgentSpan> &spans,
                            uint32_t ntables, std::vector<uint64_t> &counts);

@@ -8,10 +8,15 @@
 // the offsets alone; no frame byte is parsed, and a piece may have any length >= 0. The rules are
 // stated at corro_assemble_in (corro_hip.h).
 //
+// corro_assemble_answers_buffered adds a third piece between the two: the need's buffered frames, from
+// a second encoder call over corro_buffered_spans' output (buffered_serve.hip). The kernels that know
+// the pieces are templates over the piece count P (2 or 3); the copy only sees P * nneeds + 1 offsets.
+//
 // Kernels (wave64, 256 lanes per workgroup):
-//   k_as_check   the six offset arrays monotone and ending inside their arrays: one lane per index
+//   k_as_check   the six offset arrays (nine with P = 3) monotone and ending inside their arrays: one
+//                lane per index
 //   k_as_pieces  one lane per need (only after k_as_check passed: it reads through the offsets): the
-//                2 * nneeds piece lengths and each piece's source address
+//                P * nneeds piece lengths and each piece's source address
 //   k_as_frames  one lane per frame: frame_ans_off; one lane per need: a kept host need marks its
 //                frame (binary search of the two CSR levels; every marker stores the same 1)
 //   k_as_copy    driven from the output: a workgroup owns AS_TILE aligned 16-byte blocks of the
@@ -43,12 +48,16 @@ constexpr uint32_t AS_WIN = 512;                   // the longest window of piec
 
 struct AsDev {
     corro_assemble_in in;
+    // the buffered piece (three pieces per need, corro_assemble_answers_buffered): the second encoder's
+    uint64_t nbspans, benc_nframes, benc_nbytes;
+    const uint64_t *need_bspan_off, *bspan_frame_off, *benc_frame_off;
+    const uint8_t *benc_buf;
     uint32_t tfs;                                  // tail frame size
     unsigned long long *misc;                      // [0] error flag, [1] total bytes
     uint32_t *part;                                // one word per workgroup of the check
-    uint64_t *len;                                 // 2 * nneeds piece lengths
-    uint64_t *po;                                  // 2 * nneeds + 1 piece offsets (po[0] = 0)
-    uint64_t *psrc;                                // 2 * nneeds: the address of each piece's first byte
+    uint64_t *len;                                 // P * nneeds piece lengths (P = 2 or 3 pieces per need)
+    uint64_t *po;                                  // P * nneeds + 1 piece offsets (po[0] = 0)
+    uint64_t *psrc;                                // P * nneeds: the address of each piece's first byte
     uint64_t *need_ans_off, *frame_ans_off;        // nneeds + 1, nframes + 1
     uint8_t *frame_host;                           // nframes
 };
@@ -75,7 +84,7 @@ __device__ inline uint64_t lb64(const uint64_t *a, uint64_t len, uint64_t v) {
     return lo;
 }
 
-__global__ void k_as_check(AsDev d) {
+template <int P> __global__ void k_as_check(AsDev d) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const corro_assemble_in &in = d.in;
     bool bad = false;
@@ -91,6 +100,16 @@ __global__ void k_as_check(AsDev d) {
         if (i < in.enc_nframes) bad |= in.enc_frame_off[i] > in.enc_frame_off[i + 1];
         if (i == in.enc_nframes) bad |= in.enc_frame_off[i] > in.enc_nbytes;
     }
+    if (P == 3) {
+        if (i < in.nneeds) bad |= d.need_bspan_off[i] > d.need_bspan_off[i + 1];
+        if (i == in.nneeds) bad |= d.need_bspan_off[i] > d.nbspans;
+        if (d.nbspans) {                           // (as for the first encoder's)
+            if (i < d.nbspans) bad |= d.bspan_frame_off[i] > d.bspan_frame_off[i + 1];
+            if (i == d.nbspans) bad |= d.bspan_frame_off[i] > d.benc_nframes;
+            if (i < d.benc_nframes) bad |= d.benc_frame_off[i] > d.benc_frame_off[i + 1];
+            if (i == d.benc_nframes) bad |= d.benc_frame_off[i] > d.benc_nbytes;
+        }
+    }
     const int any = __syncthreads_or(bad ? 1 : 0);
     if (threadIdx.x == 0) d.part[blockIdx.x] = any ? 1u : 0u;
 }
@@ -103,9 +122,10 @@ __global__ void k_as_fold(const uint32_t *part, uint64_t n, unsigned long long *
     if (threadIdx.x == 0 && any) misc[0] = 1;
 }
 
-// Need t: the lengths and source addresses of pieces 2t (encoded frames) and 2t + 1 (tail frames).
+// Need t: the lengths and source addresses of its P pieces: P * t the encoded frames, with P = 3 the
+// buffered frames next, and the tail frames last.
 // Every offset read here has passed k_as_check; after a failed check the lengths are 0.
-__global__ void k_as_pieces(AsDev d) {
+template <int P> __global__ void k_as_pieces(AsDev d) {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const corro_assemble_in &in = d.in;
     if (t >= in.nneeds) return;
@@ -118,20 +138,29 @@ __global__ void k_as_pieces(AsDev d) {
         r0 = (uint64_t)d.tfs * in.need_tail_off[t];
         r1 = (uint64_t)d.tfs * in.need_tail_off[t + 1];
     }
-    d.len[2 * t] = e1 - e0;
-    d.len[2 * t + 1] = r1 - r0;
-    d.psrc[2 * t] = (uint64_t)reinterpret_cast<uintptr_t>(in.enc_buf) + e0;
-    d.psrc[2 * t + 1] = (uint64_t)reinterpret_cast<uintptr_t>(in.tail_buf) + r0;
+    d.len[P * t] = e1 - e0;
+    d.len[P * t + P - 1] = r1 - r0;
+    d.psrc[P * t] = (uint64_t)reinterpret_cast<uintptr_t>(in.enc_buf) + e0;
+    d.psrc[P * t + P - 1] = (uint64_t)reinterpret_cast<uintptr_t>(in.tail_buf) + r0;
+    if (P == 3) {
+        uint64_t b0 = 0, b1 = 0;
+        if (!d.misc[0] && d.nbspans) {
+            b0 = d.benc_frame_off[d.bspan_frame_off[d.need_bspan_off[t]]];
+            b1 = d.benc_frame_off[d.bspan_frame_off[d.need_bspan_off[t + 1]]];
+        }
+        d.len[P * t + 1] = b1 - b0;
+        d.psrc[P * t + 1] = (uint64_t)reinterpret_cast<uintptr_t>(d.benc_buf) + b0;
+    }
 }
 
 // Lane i: need_ans_off[i] (i <= nneeds), frame_ans_off[i] (i <= nframes), and need i's mark on its
 // frame. frame_host was zeroed on the stream before. Runs only after the check passed.
-__global__ void k_as_frames(AsDev d) {
+template <int P> __global__ void k_as_frames(AsDev d) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const corro_assemble_in &in = d.in;
     if (d.misc[0]) return;
-    if (i <= in.nneeds) d.need_ans_off[i] = d.po[2 * i];
-    if (i <= in.nframes) d.frame_ans_off[i] = d.po[2 * in.pair_need_off[in.frame_pair_off[i]]];
+    if (i <= in.nneeds) d.need_ans_off[i] = d.po[P * i];
+    if (i <= in.nframes) d.frame_ans_off[i] = d.po[P * in.pair_need_off[in.frame_pair_off[i]]];
     if (i < in.nneeds && in.need_keep[i] && in.need_host[i]) {
         // the pair that holds need i, then the frame that holds that pair (empty ones are stepped over)
         const uint64_t p1 = ub64(in.pair_need_off, in.npairs + 1, i);
@@ -199,7 +228,7 @@ __device__ __forceinline__ void as_tile(const uint64_t *tab, const uint64_t *src
     }
 }
 
-// buf starts `lead` bytes into block 0 of its address range; npo = 2 * nneeds + 1 piece offsets.
+// buf starts `lead` bytes into block 0 of its address range; npo = P * nneeds + 1 piece offsets.
 __global__ void __launch_bounds__(256) k_as_copy(AsDev d, uint8_t *buf, uint32_t lead, uint64_t nbytes, uint64_t nblocks,
                                                  uint64_t npo) {
     __shared__ uint64_t s_tab[AS_WIN], s_src[AS_WIN];
@@ -258,7 +287,10 @@ using namespace corro;
         if (rc_ != CORRO_OK) return rc_; \
     } while (0)
 
-extern "C" int corro_assemble_answers(corro_ctx *ctx, const corro_assemble_in *in, int mem, corro_assembled *out, int pass) {
+// P pieces per need; bin (P = 3 only): the buffered piece's arrays, in = &bin->base.
+template <int P>
+static int assemble(corro_ctx *ctx, const corro_assemble_in *in, const corro_assemble_buffered_in *bin, int mem,
+                    corro_assembled *out, int pass) {
     if (!ctx || !in || !out) return fail(CORRO_E_INVALID, "NULL argument");
     if (mem != CORRO_MEM_HOST && mem != CORRO_MEM_DEVICE) return fail(CORRO_E_INVALID, "bad mem kind");
     if (pass != 0 && pass != 1) return fail(CORRO_E_INVALID, "pass must be 0 or 1");
@@ -274,6 +306,13 @@ extern "C" int corro_assemble_answers(corro_ctx *ctx, const corro_assemble_in *i
     if (F >= (1ull << 40) || NP >= (1ull << 40) || T >= (1ull << 40) || NS >= (1ull << 40) || EF >= (1ull << 40) ||
         EB >= (1ull << 40) || NR >= (1ull << 32))
         return fail(CORRO_E_RANGE, "at most 2^40 - 1 frames, pairs, needs, spans, encoded frames and bytes, 2^32 - 1 ranges per call");
+    const uint64_t BS = P == 3 ? bin->nbspans : 0, BF = P == 3 ? bin->benc_nframes : 0, BB = P == 3 ? bin->benc_nbytes : 0;
+    if (P == 3) {
+        if (!bin->need_bspan_off || (BS && (!bin->bspan_frame_off || !bin->benc_frame_off || (BB && !bin->benc_buf))))
+            return fail(CORRO_E_INVALID, "an input array of the buffered piece is NULL");
+        if (BS >= (1ull << 40) || BF >= (1ull << 40) || BB >= (1ull << 40))
+            return fail(CORRO_E_RANGE, "at most 2^40 - 1 buffered spans, encoded frames and bytes per call");
+    }
     if (TB != NR * tfs) return fail(CORRO_E_INVALID, "tail_nbytes is not nranges frames of the payload's size");
     if (pass == 0 && (!out->need_ans_off || !out->frame_ans_off || (F && !out->frame_host)))
         return fail(CORRO_E_INVALID, "need_ans_off, frame_ans_off or frame_host is NULL");
@@ -292,23 +331,29 @@ extern "C" int corro_assemble_answers(corro_ctx *ctx, const corro_assemble_in *i
     AsDev d{};
     d.in = *in;
     d.tfs = tfs;
-    const uint64_t ncheck = std::max({F, NP, T, NS ? std::max(NS, EF) : 0}) + 1;
+    if (P == 3) {
+        d.nbspans = BS, d.benc_nframes = BF, d.benc_nbytes = BB;
+        d.need_bspan_off = bin->need_bspan_off, d.bspan_frame_off = bin->bspan_frame_off;
+        d.benc_frame_off = bin->benc_frame_off, d.benc_buf = bin->benc_buf;
+    }
+    const uint64_t ncheck = std::max({F, NP, T, NS ? std::max(NS, EF) : 0, BS ? std::max(BS, BF) : 0}) + 1;
     const uint64_t wg_check = (ncheck + 255) / 256;
     size_t temp = 0;
-    AS_TRY(prim_inclusive_sum_u64(nullptr, &temp, nullptr, nullptr, std::max<uint64_t>(2 * T, 1), s));
+    AS_TRY(prim_inclusive_sum_u64(nullptr, &temp, nullptr, nullptr, std::max<uint64_t>(P * T, 1), s));
     temp += 256;
     // (+ 32 behind a staged source buffer: the aligned loads' granules)
     const size_t stage = host ? al((F + 1) * 8) + al((NP + 1) * 8) + 2 * al(T + 1) + 2 * al((T + 1) * 8) + al((NS + 1) * 8) +
-                                    al((EF + 1) * 8) + al(EB + 32) + al(TB + 32)
+                                    al((EF + 1) * 8) + al(EB + 32) + al(TB + 32) +
+                                    (P == 3 ? al((T + 1) * 8) + al((BS + 1) * 8) + al((BF + 1) * 8) + al(BB + 32) : 0)
                               : 0;
-    AS_TRY(ctx->d_reqdec[0].ensure(256 + al(wg_check * 4) + 2 * al(2 * T * 8 + 8) + al((2 * T + 1) * 8) + al((T + 1) * 8) +
+    AS_TRY(ctx->d_reqdec[0].ensure(256 + al(wg_check * 4) + 2 * al(P * T * 8 + 8) + al((P * T + 1) * 8) + al((T + 1) * 8) +
                                    al((F + 1) * 8) + al(F + 1) + al(temp) + stage));
     Carver c0{ctx->d_reqdec[0].as<uint8_t>()};
     d.misc = c0.take<unsigned long long>(32);
     d.part = c0.take<uint32_t>(wg_check);
-    d.len = c0.take<uint64_t>(2 * T + 1);
-    d.psrc = c0.take<uint64_t>(2 * T + 1);
-    d.po = c0.take<uint64_t>(2 * T + 1);
+    d.len = c0.take<uint64_t>(P * T + 1);
+    d.psrc = c0.take<uint64_t>(P * T + 1);
+    d.po = c0.take<uint64_t>(P * T + 1);
     d.need_ans_off = c0.take<uint64_t>(T + 1);
     d.frame_ans_off = c0.take<uint64_t>(F + 1);
     d.frame_host = c0.take<uint8_t>(F + 1);
@@ -330,27 +375,36 @@ extern "C" int corro_assemble_answers(corro_ctx *ctx, const corro_assemble_in *i
         d.in.enc_frame_off = (const uint64_t *)up(in->enc_frame_off, NS ? (EF + 1) * 8 : 0, (EF + 1) * 8);
         d.in.enc_buf = (const uint8_t *)up(in->enc_buf, NS ? EB : 0, EB + 32);
         d.in.tail_buf = (const uint8_t *)up(in->tail_buf, TB, TB + 32);
+        if (P == 3) {
+            d.need_bspan_off = (const uint64_t *)up(bin->need_bspan_off, (T + 1) * 8, (T + 1) * 8);
+            d.bspan_frame_off = (const uint64_t *)up(bin->bspan_frame_off, BS ? (BS + 1) * 8 : 0, (BS + 1) * 8);
+            d.benc_frame_off = (const uint64_t *)up(bin->benc_frame_off, BS ? (BF + 1) * 8 : 0, (BF + 1) * 8);
+            d.benc_buf = (const uint8_t *)up(bin->benc_buf, BS ? BB : 0, BB + 32);
+        }
         if (!ok) return fail(CORRO_E_DEVICE, "upload of the answer pieces failed");
     }
     CORRO_HIP_TRY(hipMemsetAsync(d.misc, 0, 256, s));
     CORRO_HIP_TRY(hipMemsetAsync(d.po, 0, 8, s));
     CORRO_HIP_TRY(hipMemsetAsync(d.frame_host, 0, F + 1, s));
-    AS_LAUNCH(k_as_check, ncheck, d);
+    AS_LAUNCH(k_as_check<P>, ncheck, d);
     hipLaunchKernelGGL(k_as_fold, dim3(1), dim3(256), 0, s, (const uint32_t *)d.part, wg_check, d.misc);
     CORRO_HIP_TRY(hipGetLastError());
     if (T) {
-        AS_LAUNCH(k_as_pieces, T, d);
+        AS_LAUNCH(k_as_pieces<P>, T, d);
         size_t t = temp;
-        AS_TRY(prim_inclusive_sum_u64(tmp, &t, d.len, d.po + 1, 2 * T, s));
+        AS_TRY(prim_inclusive_sum_u64(tmp, &t, d.len, d.po + 1, P * T, s));
     }
-    CORRO_HIP_TRY(hipMemcpyAsync(d.misc + 1, d.po + 2 * T, 8, hipMemcpyDeviceToDevice, s));
-    if (pass == 0) AS_LAUNCH(k_as_frames, std::max(T, F) + 1, d);
+    CORRO_HIP_TRY(hipMemcpyAsync(d.misc + 1, d.po + P * T, 8, hipMemcpyDeviceToDevice, s));
+    if (pass == 0) AS_LAUNCH(k_as_frames<P>, std::max(T, F) + 1, d);
     unsigned long long misc[2] = {0, 0};
     CORRO_HIP_TRY(hipMemcpyAsync(misc, d.misc, sizeof(misc), hipMemcpyDeviceToHost, s));
     CORRO_HIP_TRY(hipStreamSynchronize(s));
     if (misc[0])
-        return fail(CORRO_E_INVALID, "frame_pair_off, pair_need_off, need_span_off, span_frame_off, enc_frame_off or "
-                                     "need_tail_off not monotone or ending outside its array");
+        return fail(CORRO_E_INVALID, P == 3 ? "frame_pair_off, pair_need_off, need_span_off, span_frame_off, enc_frame_off, "
+                                              "need_bspan_off, bspan_frame_off, benc_frame_off or need_tail_off not monotone "
+                                              "or ending outside its array"
+                                            : "frame_pair_off, pair_need_off, need_span_off, span_frame_off, enc_frame_off or "
+                                              "need_tail_off not monotone or ending outside its array");
     const hipMemcpyKind back = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
     if (pass == 0) {
         CORRO_HIP_TRY(hipMemcpyAsync(out->need_ans_off, d.need_ans_off, (T + 1) * 8, back, s));
@@ -370,9 +424,18 @@ extern "C" int corro_assemble_answers(corro_ctx *ctx, const corro_assemble_in *i
     const uint32_t lead = (uint32_t)(reinterpret_cast<uintptr_t>(buf) & 15);
     const uint64_t nblocks = (lead + NB + 15) / 16;
     hipLaunchKernelGGL(k_as_copy, dim3((uint32_t)((nblocks + AS_TILE - 1) / AS_TILE)), dim3(256), 0, s, d, buf, lead, NB,
-                       nblocks, 2 * T + 1);
+                       nblocks, P * T + 1);
     CORRO_HIP_TRY(hipGetLastError());
     if (host) CORRO_HIP_TRY(hipMemcpyAsync(out->buf, buf, NB, hipMemcpyDeviceToHost, s));
     CORRO_HIP_TRY(hipStreamSynchronize(s));
     return CORRO_OK;
+}
+
+extern "C" int corro_assemble_answers(corro_ctx *ctx, const corro_assemble_in *in, int mem, corro_assembled *out, int pass) {
+    return assemble<2>(ctx, in, nullptr, mem, out, pass);
+}
+
+extern "C" int corro_assemble_answers_buffered(corro_ctx *ctx, const corro_assemble_buffered_in *in, int mem,
+                                               corro_assembled *out, int pass) {
+    return assemble<3>(ctx, in ? &in->base : nullptr, in, mem, out, pass);
 }

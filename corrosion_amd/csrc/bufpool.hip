@@ -162,6 +162,13 @@ bool bufpool_usable(corro_ctx *ctx, const DevBufPool *p) { return p && (p->devic
 
 uint64_t bufpool_top(const DevBufPool *p) { return p ? p->top : 0; }
 
+bool bufpool_view(const DevBufPool *p, corro_changes *v) {
+    if (!p || !p->buf.p) return false;
+    *v = pool_view(p->buf.p, p->cap);
+    v->n = p->top;
+    return true;
+}
+
 int agent_dev_table_counts(corro_ctx *ctx, const corro_changes *dv, const std::vector<AgentSpan> &spans,
                            uint32_t ntables, std::vector<uint64_t> &counts) {
     counts.assign(ntables, 0);

@@ -1033,6 +1033,123 @@ class MergeEngine:
         return {"buf": buf[:NB], "need_ans_off": nao[:T + 1], "frame_ans_off": fao[:F + 1], "frame_host": fh[:F],
                 "nbytes": NB}
 
+    _BUFIDX_IN = (("ver_off", "ver_off", np.uint64), ("version", "idx_version", np.uint64),
+                  ("last_seq", "idx_last_seq", np.int64), ("ts", "idx_ts", np.uint64), ("on_device", "on_device", np.uint8),
+                  ("sr_off", "vsr_off", np.uint64), ("sr_start", "vsr_start", np.uint64), ("sr_end", "vsr_end", np.uint64),
+                  ("seg_off", "seg_off", np.uint64), ("seg_pool_off", "seg_pool_off", np.uint64),
+                  ("seg_seq0", "seg_seq0", np.uint32), ("seg_n", "seg_n", np.uint32))
+
+    def buffered_spans(self, bookie, dec, ext, sp, tl, idx):
+        """The buffered (partial) versions' chunks of the decoded needs as spans and rows, gathered from
+        the bookie's device row pool (corro_buffered_spans). bookie: the agent's Bookie; dec / ext / sp:
+        as for need_tails; tl: need_tails' result for the books of serve.device_buffered_index (its
+        "need_host"); idx: that index's "dev" arrays. CUDA tensors only: the pool rows stay on the
+        device. Returns the spans dict encode_changesets takes, "need_bspan_off" (nneeds + 1),
+        "nspans", "rows" (the crsql_changes fields, "ts" included) and "nrows"."""
+        import torch
+        lib = L.lib()
+        if not _is_torch(dec["kind"]):
+            raise ValueError("buffered_spans takes CUDA tensors: the pool rows are on the device")
+        T, Q, E = int(dec["nneeds"]), int(dec["nseqs"]), int(dec["nents"])
+        G = int(ext["version"].shape[0])
+        S = int(idx["ver_off"].shape[0]) - 1
+        NV = int(idx["version"].shape[0])
+        if S < 0 or int(idx["sr_off"].shape[0]) != NV + 1 or int(idx["seg_off"].shape[0]) != NV + 1:
+            raise ValueError("ver_off holds nsites + 1 offsets, sr_off and seg_off one per version + 1")
+        r = L.BufSpansIn()
+        r.nneeds, r.nseqs, r.nents, r.ngroups, r.idx_nsites, r.idx_nver = T, Q, E, G, S, NV
+        r.idx_nsr, r.idx_nseg = int(idx["sr_start"].shape[0]), int(idx["seg_pool_off"].shape[0])
+        keep = []
+        fields = [(dec, "kind", "kind", np.uint8, T), (dec, "start", "start", np.uint64, T), (dec, "end", "end", np.uint64, T),
+                  (dec, "sr_off", "sr_off", np.uint64, T), (dec, "sr_n", "sr_n", np.uint64, T),
+                  (dec, "s_start", "s_start", np.uint64, Q), (dec, "s_end", "s_end", np.uint64, Q),
+                  (dec, "need_keep", "need_keep", np.uint8, T), (dec, "need_site", "need_site", np.uint32, T),
+                  (dec, "need_ent_off", "need_ent_off", np.uint64, T + 1), (sp, "in_state", "in_state", np.uint8, T),
+                  (tl, "need_host", "need_host", np.uint8, T), (ext, "grp_off", "grp_off", np.uint64, E + 1),
+                  (ext, "version", "version", np.int64, G)]
+        fields += [(idx, k, dst, dt, None) for k, dst, dt in self._BUFIDX_IN]
+        for src, k, dst, dt, cnt in fields:
+            a, p = self._in_field(src[k], dt, True, k, cnt)
+            keep.append(a)
+            setattr(r, dst, p)
+        for k, n in (("last_seq", NV), ("ts", NV), ("on_device", NV), ("sr_end", r.idx_nsr), ("seg_seq0", r.idx_nseg),
+                     ("seg_n", r.idx_nseg)):
+            if int(idx[k].shape[0]) != n:
+                raise ValueError(f"index field {k} must hold {n} entries")
+        alloc, ptr, sync = self._two_pass_io(True, dec["kind"].device)
+        o = L.BufSpansOut()
+        nbo = alloc(T + 1, np.uint64)
+        o.need_bspan_off = ptr(nbo)
+        sync()
+        L.check(lib.corro_buffered_spans(self._h, bookie._h, C.byref(r), L.CORRO_MEM_DEVICE, C.byref(o), 0))
+        N, R = int(o.nspans), int(o.nrows)
+        res = {}
+        for k, dt in (("site", np.uint32), ("version", np.int64), ("last_seq", np.uint64), ("ts", np.uint64),
+                      ("seq_start", np.uint64), ("seq_end", np.uint64), ("row_off", np.uint64), ("row_count", np.uint64)):
+            res[k] = alloc(N, dt)
+            setattr(o, k, ptr(res[k]))
+        tdt = {1: torch.uint8, 4: torch.int32, 8: torch.int64}
+        rows = {k: torch.empty(max(R, 1), dtype=tdt[np.dtype(dt).itemsize], device=dec["kind"].device)
+                for k, dt in ROW_FIELDS.items()}
+        for k, a in rows.items():
+            setattr(o.rows, k, ptr(a))
+        sync()
+        L.check(lib.corro_buffered_spans(self._h, bookie._h, C.byref(r), L.CORRO_MEM_DEVICE, C.byref(o), 1))
+        res = {k: a[:N] for k, a in res.items()}
+        res["need_bspan_off"], res["nspans"] = nbo[:T + 1], N
+        res["rows"], res["nrows"] = {k: a[:R] for k, a in rows.items()}, R
+        return res
+
+    def assemble_answers_buffered(self, dec, sp, enc, bsp, benc, tl, payload=0):
+        """assemble_answers with the buffered frames as a third piece between a need's encoded frames
+        and its Empty tail frames (corro_assemble_answers_buffered). bsp: buffered_spans' result (its
+        "need_bspan_off"); benc: encode_changesets' result for bsp's spans and rows (None when bsp
+        holds no span). The other arguments and the result are assemble_answers'."""
+        lib = L.lib()
+        on_dev = _is_torch(dec["frame_pair_off"])
+        F, NP, T = int(dec["nframes"]), int(dec["npairs"]), int(dec["nneeds"])
+        NS, NR, BS = int(sp["nspans"]), int(tl["nranges"]), int(bsp["nspans"])
+        rb = L.AssembleBufferedIn()
+        r = rb.base
+        r.nframes, r.npairs, r.nneeds, r.nspans, r.nranges, r.payload = F, NP, T, NS, NR, int(payload)
+        r.enc_nframes, r.enc_nbytes = (int(enc["nframes"]), int(enc["nbytes"])) if NS else (0, 0)
+        r.tail_nbytes = int(tl["buf"].shape[0])
+        rb.nbspans = BS
+        rb.benc_nframes, rb.benc_nbytes = (int(benc["nframes"]), int(benc["nbytes"])) if BS else (0, 0)
+        keep = []
+        fields = [(r, dec, "frame_pair_off", "frame_pair_off", np.uint64, F + 1),
+                  (r, dec, "pair_need_off", "pair_need_off", np.uint64, NP + 1),
+                  (r, dec, "need_keep", "need_keep", np.uint8, T), (r, sp, "need_span_off", "need_span_off", np.uint64, T + 1),
+                  (r, tl, "need_tail_off", "need_tail_off", np.uint64, T + 1), (r, tl, "need_host", "need_host", np.uint8, T),
+                  (r, tl, "buf", "tail_buf", np.uint8, None),
+                  (rb, bsp, "need_bspan_off", "need_bspan_off", np.uint64, T + 1)]
+        if NS:
+            fields += [(r, enc, "span_frame_off", "span_frame_off", np.uint64, NS + 1),
+                       (r, enc, "frame_off", "enc_frame_off", np.uint64, r.enc_nframes + 1),
+                       (r, enc, "buf", "enc_buf", np.uint8, r.enc_nbytes)]
+        if BS:
+            fields += [(rb, benc, "span_frame_off", "bspan_frame_off", np.uint64, BS + 1),
+                       (rb, benc, "frame_off", "benc_frame_off", np.uint64, rb.benc_nframes + 1),
+                       (rb, benc, "buf", "benc_buf", np.uint8, rb.benc_nbytes)]
+        for st, src, k, dst, dt, cnt in fields:
+            a, p = self._in_field(src[k], dt, on_dev, k, cnt)
+            keep.append(a)
+            setattr(st, dst, p)
+        alloc, ptr, sync = self._two_pass_io(on_dev, dec["frame_pair_off"].device if on_dev else None)
+        mem = L.CORRO_MEM_DEVICE if on_dev else L.CORRO_MEM_HOST
+        o = L.Assembled()
+        nao, fao, fh = alloc(T + 1, np.uint64), alloc(F + 1, np.uint64), alloc(F, np.uint8)
+        o.need_ans_off, o.frame_ans_off, o.frame_host = ptr(nao), ptr(fao), ptr(fh)
+        sync()
+        L.check(lib.corro_assemble_answers_buffered(self._h, C.byref(rb), mem, C.byref(o), 0))
+        NB = int(o.nbytes)
+        buf = alloc(NB, np.uint8)
+        o.buf = ptr(buf)
+        sync()
+        L.check(lib.corro_assemble_answers_buffered(self._h, C.byref(rb), mem, C.byref(o), 1))
+        return {"buf": buf[:NB], "need_ans_off": nao[:T + 1], "frame_ans_off": fao[:F + 1], "frame_host": fh[:F],
+                "nbytes": NB}
+
     # ---- sync need diff -------------------------------------------------------------------
     def compute_needs(self, entries):
         """Batched compute_available_needs over CSR entries (see corrosion_amd.sync)."""

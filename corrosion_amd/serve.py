@@ -423,6 +423,177 @@ def device_buffered(agent, dev):
     return {"buf_off": up(buf_off), "buf_version": up(bv)}
 
 
+_BUFIDX_FIELDS = (("ver_off", np.uint64, "nsites1"), ("version", np.uint64, "nver"), ("last_seq", np.int64, "nver"),
+                  ("ts", np.uint64, "nver"), ("on_device", np.uint8, "nver"), ("sr_off", np.uint64, "nver1"),
+                  ("sr_start", np.uint64, "nsr"), ("sr_end", np.uint64, "nsr"), ("seg_off", np.uint64, "nver1"),
+                  ("seg_pool_off", np.uint64, "nseg"), ("seg_seq0", np.uint32, "nseg"), ("seg_n", np.uint32, "nseg"),
+                  ("tail_gap_off", np.uint64, "nsites1"), ("tail_gap_start", np.uint64, "ntail_gap"),
+                  ("tail_gap_end", np.uint64, "ntail_gap"), ("host_buf_off", np.uint64, "nsites1"),
+                  ("host_buf_version", np.uint64, "nhost_buf"))
+
+
+def buffered_index(agent):
+    """corro_bookie_buffered_index over the engine's registered sites, as numpy arrays: one call in
+    place of device_buffered's probe per site. Nothing is materialised: pool keys stay in the pool.
+    Per site ordinal a CSR ("ver_off") over its buffered versions ("version", ascending) with
+    "last_seq" (-1 = no seq bookkeeping), "ts", their seq ranges ("sr_off", "sr_start", "sr_end"),
+    "on_device" and the on_device versions' pool segments ("seg_off", "seg_pool_off", "seg_seq0",
+    "seg_n"); and the books need_tails takes with it: "tail_gap_off" / "_start" / "_end" (needed()
+    united with the on_device versions) and "host_buf_off" / "host_buf_version" (the others). The pool
+    offsets hold until the bookie's next process_multiple_changes / process_fully_buffered_changes."""
+    ids = agent.engine.site_ids()
+    S = len(ids)
+    raw = np.frombuffer(b"".join(ids), np.uint8).copy() if S else np.zeros(1, np.uint8)
+    o = L.BufferedIndex()
+    L.check(L.lib().corro_bookie_buffered_index(agent.bookie._h, raw.ctypes.data, S, C.byref(o), 0))
+    tot = {k: int(getattr(o, k)) for k in ("nver", "nsr", "nseg", "ntail_gap", "nhost_buf")}
+    tot["nsites1"], tot["nver1"] = S + 1, tot["nver"] + 1
+    res = {}
+    for k, dt, size in _BUFIDX_FIELDS:
+        res[k] = np.zeros(max(tot[size], 1), dt)
+        setattr(o, k, res[k].ctypes.data)
+    L.check(L.lib().corro_bookie_buffered_index(agent.bookie._h, raw.ctypes.data, S, C.byref(o), 1))
+    return {k: res[k][:tot[size]] for k, _dt, size in _BUFIDX_FIELDS}
+
+
+def device_buffered_index(agent, dev):
+    """buffered_index for the device path: {"host": the numpy arrays, "dev": the version / seq range /
+    segment arrays as CUDA tensors on dev (what MergeEngine.buffered_spans reads), "book": the derived
+    books in need_tails' names ("gap_off", "gap_start", "gap_end", "buf_off", "buf_version"), CUDA
+    tensors}. All of it goes up in one copy."""
+    import torch
+    h = buffered_index(agent)
+    names = [k for k, _dt, _s in _BUFIDX_FIELDS]
+    off, total = {}, 0
+    for k in names:                                            # one staging buffer, 8-byte aligned slices
+        off[k] = total
+        total += (h[k].nbytes + 7) // 8 * 8
+    stage = np.zeros(max(total, 8), np.uint8)
+    for k in names:
+        stage[off[k]:off[k] + h[k].nbytes] = h[k].view(np.uint8)
+    d = torch.from_numpy(stage).to(dev)
+    tdt = {1: torch.uint8, 4: torch.int32, 8: torch.int64}
+    t = {k: d[off[k]:off[k] + h[k].nbytes].view(tdt[h[k].itemsize]) for k in names}
+    book = {"gap_off": t["tail_gap_off"], "gap_start": t["tail_gap_start"], "gap_end": t["tail_gap_end"],
+            "buf_off": t["host_buf_off"], "buf_version": t["host_buf_version"]}
+    return {"host": h, "dev": {k: t[k] for k in names[:12]}, "book": book}
+
+
+def handle_request_frames_buffered(agent, buf, frame_off, max_buf_size=MAX_CHANGES_BYTES_PER_MESSAGE, payload=0,
+                                   cluster_id=0, timings=None):
+    """handle_request_frames_assembled with the buffered (partial) versions served from the device row
+    pool: the same arguments, the same (frame_status, answers), byte for byte.
+
+    A need whose buffered versions all lie in the bookie's pool (what process_frames buffers from
+    canonical partial changesets) no longer goes back to the host walk, which would read the
+    version's rows out of the pool for good. Stages: decode -> extract -> spans -> encode -> tails
+    against device_buffered_index's derived books (the pool versions count as gaps there, so only a
+    need that touches a host-row version keeps need_host) -> buffered_spans (the buffered chunks as
+    spans, their rows gathered from the pool) -> a second encode -> assemble_answers_buffered (per
+    need: state frames, buffered frames, Empty frames). The request screen keeps the real gaps. A need
+    still flagged need_host takes _bookie_messages, spliced in at need_ans_off[t + 1] as in
+    handle_request_frames_assembled. timings: that function's keys plus "buffered" (buffered_spans
+    and the second encode; the index call counts under "tails")."""
+    import time
+
+    import torch
+
+    from . import wire
+    eng = agent.engine
+    dev = torch.device("cuda", eng.device)
+    t0 = time.perf_counter()
+
+    def lap(name):
+        nonlocal t0
+        if timings is not None:
+            torch.cuda.synchronize(dev)
+            t1 = time.perf_counter()
+            timings[name] = timings.get(name, 0.0) + (t1 - t0)
+            t0 = t1
+
+    if not torch.is_tensor(buf):
+        buf = torch.from_numpy(np.frombuffer(bytes(buf), np.uint8).copy()).to(dev)
+    if not torch.is_tensor(frame_off):
+        frame_off = torch.from_numpy(np.ascontiguousarray(frame_off, np.uint64).view(np.int64)).to(dev)
+    book = device_book(agent, dev)
+    lap("book")
+    dec = eng.decode_requests(buf, frame_off, book)
+    lap("decode")
+    status = dec["frame_status"].cpu().numpy()
+    F, T = dec["nframes"], dec["nneeds"]
+    answers = [b""] * F
+    if T == 0 or dec["nents"] == 0:
+        return status, answers
+    ext = eng.extract_changes({"site": dec["ent_site"], "start": dec["ent_start"], "end": dec["ent_end"],
+                               "seq_start": dec["ent_seq_start"], "seq_end": dec["ent_seq_end"]})
+    lap("extract")
+    sp = eng.need_spans(dec, ext)
+    lap("spans")
+    span_keys = ("site", "version", "last_seq", "ts", "seq_start", "seq_end", "row_off", "row_count")
+    enc = eng.encode_changesets({k: sp[k] for k in span_keys}, ext["rows"], max_buf_size, payload, cluster_id)
+    lap("encode")
+    idx = device_buffered_index(agent, dev)
+    tl = eng.need_tails(dec, ext, sp, idx["book"], payload, cluster_id)
+    lap("tails")
+    bsp = eng.buffered_spans(agent.bookie, dec, ext, sp, tl, idx["dev"])
+    benc = None
+    if bsp["nspans"]:
+        benc = eng.encode_changesets({k: bsp[k] for k in span_keys}, bsp["rows"], max_buf_size, payload, cluster_id)
+    lap("buffered")
+    asm = eng.assemble_answers_buffered(dec, sp, enc, bsp, benc, tl, payload)
+    lap("assemble")
+    fao, fhost = asm["frame_ans_off"].cpu().numpy(), asm["frame_host"].cpu().numpy()
+    pinned = getattr(eng, "_answer_staging", None)             # pinned, kept with the engine and grown
+    if pinned is None or pinned.numel() < asm["nbytes"]:
+        pinned = eng._answer_staging = torch.empty(max(asm["nbytes"], 1), dtype=torch.uint8, pin_memory=True)
+    pinned[:asm["nbytes"]].copy_(asm["buf"])
+    out = memoryview(pinned.numpy())[:asm["nbytes"]]
+    hosted = np.flatnonzero(fhost)
+    if len(hosted):                                            # what the host bookie's walk needs
+        h = {k: dec[k].cpu().numpy() for k in ("frame_pair_off", "pair_need_off", "pair_actor", "kind", "start", "end",
+                                               "sr_off", "sr_n", "s_start", "s_end", "need_keep", "need_ent_off")}
+        ins, need_host = sp["in_state"].cpu().numpy(), tl["need_host"].cpu().numpy()
+        grp_off, versions = ext["grp_off"].cpu().numpy(), ext["version"].cpu().numpy()
+        nao = asm["need_ans_off"].cpu().numpy()
+    lap("readback")
+    for f in np.flatnonzero(fhost == 0):
+        a, b = int(fao[f]), int(fao[f + 1])
+        if b > a:
+            answers[f] = bytes(out[a:b])
+    if len(hosted):
+        site_ids = dict(enumerate(eng.site_ids()))
+        actors = h["pair_actor"].tobytes()
+    for f in hosted:
+        parts = []
+        for p in range(int(h["frame_pair_off"][f]), int(h["frame_pair_off"][f + 1])):
+            actor = actors[16 * p:16 * p + 16]
+            t0n, t1n = int(h["pair_need_off"][p]), int(h["pair_need_off"][p + 1])
+            lo = int(nao[t0n])                                 # the device bytes not yet taken
+            for t in range(t0n, t1n):
+                if not h["need_keep"][t] or not need_host[t]:
+                    continue
+                parts.append(bytes(out[lo:int(nao[t + 1])]))   # up to and with this need's encoded piece
+                lo = int(nao[t + 1])
+                k = int(h["need_ent_off"][t])
+                if h["kind"][t] == 0:
+                    need = NeedFull(int(h["start"][t]), int(h["end"][t]))
+                    found = {int(v) for v in versions[int(grp_off[k]):int(grp_off[k + 1])]}
+                else:
+                    q0 = int(h["sr_off"][t])
+                    need = NeedPartial(int(h["start"][t]), tuple((int(h["s_start"][q]), int(h["s_end"][q]))
+                                                                 for q in range(q0, q0 + int(h["sr_n"][t]))))
+                    found = set()
+                msgs = _bookie_messages(agent, actor, need, found, bool(ins[t]), site_ids, max_buf_size)
+                if payload == wire.PAYLOAD_SYNC:
+                    parts.append(wire.frames(msgs, wire.PAYLOAD_SYNC))
+                else:
+                    parts.append(b"".join(wire.frame(wire.encode_uni_change(cv, cluster_id)) for cv in msgs))
+            parts.append(bytes(out[lo:int(nao[t1n])]))
+        answers[f] = b"".join(parts)
+    lap("bookie")
+    return status, answers
+
+
 def handle_request_frames(agent, buf, frame_off, max_buf_size=MAX_CHANGES_BYTES_PER_MESSAGE, payload=0, cluster_id=0,
                           timings=None):
     """process_sync + handle_need from the request bytes to the response bytes (peer/mod.rs:791-905,

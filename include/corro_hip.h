@@ -1040,6 +1040,146 @@ typedef struct {
 
 int corro_assemble_answers(corro_ctx *ctx, const corro_assemble_in *in, int mem, corro_assembled *out, int pass);
 
+/* ------------------------------------------------------------------ buffered versions, served from the device */
+
+/* The bookie's buffered (partial) versions as one index, for serving them where their rows lie: the
+ * device row pool that corro_process_multiple_changes fills from canonical partial changesets of a
+ * device batch. Host side; nothing is materialised: no pool row is read and no key changes its form.
+ *
+ * actor_ids: nsites ids of 16 bytes, in site-ordinal order (corro_site_ids). Per site a CSR over its
+ * buffered versions, ascending: the set corro_bookie_buffered_versions gives over every version. Per
+ * version: last_seq (-1 = the version has no __corro_seq_bookkeeping row), ts and its seq ranges
+ * ascending, as corro_bookie_seq_bookkeeping gives them; on_device = 1 when the key holds pool
+ * segments only (no host row, no segment whose copy is pending) and the version has a
+ * __corro_seq_bookkeeping row, else 0; and for an on_device version its pool segments in seq0 order:
+ * pool rows [seg_pool_off, seg_pool_off + seg_n) hold the seqs seg_seq0 .. seg_seq0 + seg_n - 1. A
+ * version with on_device = 0 lists no segment.
+ * Lifetime: the pool offsets are valid until the next corro_process_multiple_changes or
+ * corro_process_fully_buffered on the bookie (the pool compacts when it reserves room), or any call
+ * that reads the version's rows on the host (corro_bookie_buffered, corro_bookie_buffered_value).
+ *
+ * The two books corro_need_tails takes when the on_device versions are answered from the device:
+ *   tail_gap_*  per site, needed() united with the on_device buffered versions, canonical again
+ *               (sorted, disjoint, touching runs merged): given as the gaps, the tails leave those
+ *               versions to corro_buffered_spans instead of flagging the need for the host;
+ *   host_buf_*  per site, the buffered versions with on_device = 0, ascending: given as the buffered
+ *               versions, a need that touches one keeps need_host = 1.
+ * (corro_decode_requests still screens against the real needed() gaps.)
+ *
+ * Two passes: pass 0 sets the five counts; the caller allocates (every *_off array holds its count + 1
+ * entries); pass 1 fills the arrays (counts that differ from the bookie's: CORRO_E_INVALID, nothing
+ * written). */
+typedef struct {
+    uint64_t nver, nsr, nseg, ntail_gap, nhost_buf;   /* pass 0 outputs, pass 1 inputs */
+    uint64_t *ver_off;                     /* nsites + 1 */
+    uint64_t *version;                     /* nver */
+    int64_t *last_seq;                     /* nver: -1 = no __corro_seq_bookkeeping row */
+    uint64_t *ts;                          /* nver */
+    uint8_t *on_device;                    /* nver */
+    uint64_t *sr_off;                      /* nver + 1 */
+    uint64_t *sr_start, *sr_end;           /* nsr */
+    uint64_t *seg_off;                     /* nver + 1 */
+    uint64_t *seg_pool_off;                /* nseg */
+    uint32_t *seg_seq0, *seg_n;            /* nseg */
+    uint64_t *tail_gap_off;                /* nsites + 1 */
+    uint64_t *tail_gap_start, *tail_gap_end;   /* ntail_gap */
+    uint64_t *host_buf_off;                /* nsites + 1 */
+    uint64_t *host_buf_version;            /* nhost_buf */
+} corro_buffered_index;
+
+int corro_bookie_buffered_index(corro_bookie *bk, const uint8_t *actor_ids, uint32_t nsites, corro_buffered_index *out,
+                                int pass);
+
+/* The buffered chunks of handle_need (peer/mod.rs:458-542, :598-712) as spans and rows for a second
+ * corro_encode_changesets call, from the decoded needs, the extraction's groups, in_state of
+ * corro_need_spans, need_host of a corro_need_tails call given the index's tail_gap_* / host_buf_*
+ * books, and a device copy of the index. The rows are gathered from the bookie's pool; `bk` is used for
+ * that alone. For a need with need_keep = 1 and need_host = 0 whose site is below idx_nsites, with F
+ * the versions of the groups of a Full need's one entry:
+ *   - a Full need: for every on_device version v of its site in start ..= end that is not in F,
+ *     ascending, and every seq range (rs, re) of v, ascending: one span { site, v, last_seq, ts,
+ *     seq_start = rs, seq_end = re } whose rows are the pool rows of v with seq in rs ..= re;
+ *   - a Partial need with in_state = 0 whose version is an on_device one: for every requested range
+ *     (qs, qe) in wire order and every seq range (rs, re) of the version, ascending, with
+ *     (qs <= rs <= qe) or (rs <= qs and re >= qe) or (rs <= qe and re >= qe) or (qs <= re <= qe): one span
+ *     over max(rs, qs) ..= min(re, qe) (it may be inverted: it then has no row);
+ *   - any other need gives no span.
+ * A span's rows are the intersections of its seq interval with the version's segments in seq0 order,
+ * seq ascending; segments may leave holes and a span may have no row.
+ *
+ * Two passes: pass 0 sets nspans / nrows and fills need_bspan_off, the caller allocates, pass 1 walks
+ * again and fills the span arrays and the rows (totals that differ from pass 0's: CORRO_E_INVALID).
+ * mem must be CORRO_MEM_DEVICE: the pool rows are on the device and stay there. Everything is
+ * validated before anything is read through an offset, and a failed call writes nothing:
+ * CORRO_E_INVALID for a NULL struct or a missing array, a mem other than CORRO_MEM_DEVICE, a bad pass,
+ * a kind above 1, need_ent_off / grp_off / ver_off / vsr_off / seg_off that are not monotone or leave
+ * nents / ngroups / idx_nver / idx_nsr / idx_nseg, a kept need whose entry count is not its kind's,
+ * a Partial need's seq ranges outside nseqs, versions of one site that are not strictly ascending,
+ * segments of one version that overlap or are not in seq0 order, segments given when the bookie has no
+ * pool or its pool lies on another device, or a segment that passes the pool's top;
+ * CORRO_E_RANGE for 2^40 or more of a count. The state is not read; a poisoned context is served. */
+typedef struct {
+    uint64_t nneeds, nseqs, nents, ngroups;
+    const uint8_t *kind;                   /* nneeds: corro_reqdec_out's need arrays */
+    const uint64_t *start, *end;
+    const uint64_t *sr_off, *sr_n;
+    const uint64_t *s_start, *s_end;       /* nseqs */
+    const uint8_t *need_keep;
+    const uint32_t *need_site;
+    const uint64_t *need_ent_off;          /* nneeds + 1 */
+    const uint8_t *in_state;               /* nneeds: corro_spans_out's */
+    const uint8_t *need_host;              /* nneeds: corro_tails_out's */
+    const uint64_t *grp_off;               /* nents + 1: corro_extract_out's group arrays */
+    const int64_t *version;                /* ngroups */
+    /* the index: corro_buffered_index's arrays, copied to the device */
+    uint32_t idx_nsites;
+    uint64_t idx_nver, idx_nsr, idx_nseg;
+    const uint64_t *ver_off;               /* idx_nsites + 1 */
+    const uint64_t *idx_version;           /* idx_nver */
+    const int64_t *idx_last_seq;
+    const uint64_t *idx_ts;
+    const uint8_t *on_device;
+    const uint64_t *vsr_off;               /* idx_nver + 1: the index's sr_off */
+    const uint64_t *vsr_start, *vsr_end;   /* idx_nsr */
+    const uint64_t *seg_off;               /* idx_nver + 1 */
+    const uint64_t *seg_pool_off;          /* idx_nseg */
+    const uint32_t *seg_seq0, *seg_n;
+} corro_bufspans_in;
+
+typedef struct {
+    uint64_t nspans, nrows;                /* pass 0 outputs, pass 1 inputs */
+    uint64_t *need_bspan_off;              /* nneeds + 1 (pass 0) */
+    uint32_t *site;                        /* nspans: corro_encode_in's span arrays */
+    int64_t *version;
+    uint64_t *last_seq, *ts, *seq_start, *seq_end, *row_off, *row_count;
+    corro_rows rows;                       /* nrows each; every array is written */
+} corro_bufspans_out;
+
+int corro_buffered_spans(corro_ctx *ctx, corro_bookie *bk, const corro_bufspans_in *in, int mem, corro_bufspans_out *out,
+                         int pass);
+
+/* corro_assemble_answers with three pieces per need, in this order: the need's encoded state frames,
+ * its buffered frames -- benc_buf[ benc_frame_off[bspan_frame_off[need_bspan_off[t]]] ..
+ * benc_frame_off[bspan_frame_off[need_bspan_off[t + 1]]] ), the second corro_encode_changesets call
+ * over corro_buffered_spans' output -- and its Empty tail frames. `base` is read exactly as
+ * corro_assemble_answers reads its input, and the outputs are corro_assembled's: with every buffered
+ * piece empty the buffer and the offsets are those of corro_assemble_answers. The same two passes,
+ * the same validation and failure rules; the three buffered offset arrays are checked like their
+ * neighbours (need_bspan_off <= nbspans, bspan_frame_off <= benc_nframes, benc_frame_off <=
+ * benc_nbytes; need_bspan_off is always read, the encoder's arrays only with nbspans > 0). */
+typedef struct {
+    corro_assemble_in base;
+    uint64_t nbspans;                      /* corro_bufspans_out's nspans */
+    const uint64_t *need_bspan_off;        /* nneeds + 1 */
+    uint64_t benc_nframes, benc_nbytes;    /* the second corro_encoded's nframes / nbytes */
+    const uint64_t *bspan_frame_off;       /* nbspans + 1: its span_frame_off */
+    const uint64_t *benc_frame_off;        /* benc_nframes + 1: its frame_off */
+    const uint8_t *benc_buf;               /* benc_nbytes: its buf */
+} corro_assemble_buffered_in;
+
+int corro_assemble_answers_buffered(corro_ctx *ctx, const corro_assemble_buffered_in *in, int mem, corro_assembled *out,
+                                    int pass);
+
 #ifdef __cplusplus
 }
 #endif
