@@ -131,6 +131,7 @@ __global__ void k_wire_hdr(WireDev d) {
     } else {
         if (r.u32() != 0 || r.u32() != 0 || r.u32() != 0) st = ST_NOT_CHANGESET;  // UniPayload::V1/Broadcast/Change
     }
+    if (r.bad) st = CORRO_E_INVALID;   // a frame that ends inside its tags is malformed, not another message
     uint64_t alo = 0, ahi = 0;
     if (!st) {
         alo = r.u64();

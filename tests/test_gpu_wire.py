@@ -27,7 +27,7 @@ def rand_changes(rng, n, actor, version):
         elif r < 0.4:
             val = int(rng.integers(-(1 << 62), 1 << 62))
         elif r < 0.55:
-            val = float(rng.choice([0.0, -2.5, 1e300, 3.25]))
+            val = float(rng.choice([0.0, -2.5, 1e300, 3.25, float("nan"), float("inf"), float("-inf")]))
         elif r < 0.75:
             val = "".join(chr(97 + int(x)) for x in rng.integers(0, 26, int(rng.integers(0, 41))))
         elif r < 0.9:  # (values past 16 bytes travel as val_off / val_size into the frame bytes)
