@@ -45,6 +45,7 @@ EXPORTS = [
     "corro_plan_requests", "corro_decode_requests", "corro_need_spans",
     "corro_need_tails", "corro_assemble_answers",
     "corro_bookie_buffered_index", "corro_buffered_spans", "corro_assemble_answers_buffered",
+    "corro_decode_states",
 ]
 
 CORRO_CS_FULL, CORRO_CS_EMPTY, CORRO_CS_EMPTY_SET = 0, 1, 2
@@ -170,6 +171,18 @@ class ReqDecOut(C.Structure):
         "frame_status", "frame_pair_off", "pair_actor", "pair_site", "pair_need_off", "kind", "start", "end",
         "sr_off", "sr_n", "s_start", "s_end", "need_site", "need_keep", "need_ent_off", "ent_site", "ent_start",
         "ent_end", "ent_seq_start", "ent_seq_end", "ent_need")]
+
+
+class StateDecIn(C.Structure):
+    _fields_ = [("buf", C.c_void_p), ("len", C.c_uint64), ("nframes", C.c_uint64), ("frame_off", C.c_void_p),
+                ("npairs", C.c_uint64), ("pair_ours", C.c_void_p), ("pair_theirs", C.c_void_p)]
+
+
+class StateDecOut(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("n", "ntn", "ntp", "ntps", "non", "nop", "nops", "nunregistered")] + [
+        (k, C.c_void_p) for k in ("frame_status", "frame_actor", "frame_has_ts", "frame_ts", "pair_status",
+                                  "pair_ent_off") + tuple(k for k, _ in SyncEntries._fields_[1:]) + (
+                                      "entry_pair", "entry_actor", "entry_site")]
 
 
 class SpansIn(C.Structure):
@@ -320,6 +333,7 @@ def lib():
         "corro_plan_requests": (i32, [vp, C.POINTER(RequestIn), i32, C.POINTER(Requests), i32]),
         "corro_decode_requests": (i32, [vp, C.POINTER(ReqDecIn), i32, C.POINTER(ReqDecOut), i32]),
         "corro_need_spans": (i32, [vp, C.POINTER(SpansIn), i32, C.POINTER(SpansOut), i32]),
+        "corro_decode_states": (i32, [vp, C.POINTER(StateDecIn), i32, C.POINTER(StateDecOut), i32]),
         "corro_need_tails": (i32, [vp, C.POINTER(TailsIn), i32, C.POINTER(TailsOut), i32]),
         "corro_assemble_answers": (i32, [vp, C.POINTER(AssembleIn), i32, C.POINTER(Assembled), i32]),
         "corro_bookie_buffered_index": (i32, [vp, vp, u32, C.POINTER(BufferedIndex), i32]),

@@ -291,6 +291,9 @@ struct corro_ctx {
     // [0] staged host inputs, per-frame / per-need counts, offsets and rocPRIM temp, [1] staged host
     // outputs (need tails: and the site of every range)
     corro::DevBuf d_reqdec[2];
+    // state decode (state_decode.hip): [0] staged host inputs, per-frame / per-pair counts, offsets and
+    // rocPRIM temp, [1] the per-frame offset and join tables, [2] staged host outputs
+    corro::DevBuf d_statedec[3];
     bool wire_schema_ready = false;
     const uint8_t *wire_names = nullptr;
     const uint32_t *wire_toff = nullptr, *wire_tlen = nullptr, *wire_tbase = nullptr, *wire_tn = nullptr,

@@ -418,6 +418,132 @@ def plan_sync_requests(engine, sessions, chunk=10, drain=10):
     return split_requests(res, groups, len(sessions), [len(s) for s in sessions])
 
 
+_ENT_KEYS = tuple(k for k, _ in L.SyncEntries._fields_[1:])
+# corro_statedec_out's arrays: name -> (element type, total its length comes from, extra elements)
+_STATE_FRAME = (("frame_status", "int32", 1), ("frame_actor", "uint8", 16), ("frame_has_ts", "uint8", 1),
+                ("frame_ts", "int64", 1))
+_STATE_ENT = {"their_head": ("n", 0), "our_head": ("n", 0), "tn_off": ("n", 1), "tn_start": ("ntn", 0), "tn_end": ("ntn", 0),
+              "tp_off": ("n", 1), "tp_ver": ("ntp", 0), "tps_off": ("ntp", 1), "tps_start": ("ntps", 0),
+              "tps_end": ("ntps", 0), "on_off": ("n", 1), "on_start": ("non", 0), "on_end": ("non", 0),
+              "op_off": ("n", 1), "op_ver": ("nop", 0), "ops_off": ("nop", 1), "ops_start": ("nops", 0),
+              "ops_end": ("nops", 0)}
+_STATE_TOTALS = ("n", "ntn", "ntp", "ntps", "non", "nop", "nops", "nunregistered")
+
+
+class _StateFrames:
+    """corro_decode_states over one set of frames and pairs: pass 0 once, pass 1 as often as asked."""
+
+    def __init__(self, engine, buf, frame_off, pairs, device):
+        self.engine, self.device = engine, device
+        if device:
+            import torch
+            self.torch = torch
+            dev = buf.device
+            npdt = {torch.uint8: np.uint8, torch.int32: np.int32, torch.int64: np.int64}
+            as_t = lambda a, dt: a.to(device=dev, dtype=dt).contiguous() if hasattr(a, "to") else torch.from_numpy(
+                np.asarray(a).astype(npdt[dt])).to(dev)
+            self.buf = as_t(buf, torch.uint8)
+            self.frame_off = as_t(frame_off, torch.int64)
+            pr = as_t(pairs, torch.int32).reshape(-1, 2)
+            self.ours, self.theirs = pr[:, 0].contiguous(), pr[:, 1].contiguous()
+            self.count = lambda a: int(a.numel())
+            self.ptr = lambda a: a.data_ptr() if a.numel() else None
+            self.new = lambda m, dt: torch.empty(max(m, 1), dtype=getattr(torch, dt), device=dev)
+        else:
+            self.buf = np.frombuffer(bytes(buf), np.uint8) if isinstance(buf, (bytes, bytearray)) else np.ascontiguousarray(
+                buf, np.uint8)
+            self.frame_off = np.ascontiguousarray(frame_off, np.uint64)
+            pr = np.asarray(pairs, np.int64).reshape(-1, 2)
+            self.ours, self.theirs = np.ascontiguousarray(pr[:, 0], np.uint32), np.ascontiguousarray(pr[:, 1], np.uint32)
+            self.count = lambda a: int(a.size)
+            self.ptr = lambda a: a.ctypes.data if a.size else None
+            self.new = lambda m, dt: np.zeros(max(m, 1), dtype=dt)
+        r = L.StateDecIn()
+        r.buf, r.len = self.ptr(self.buf), self.count(self.buf)
+        r.nframes, r.frame_off = self.count(self.frame_off) - 1, self.ptr(self.frame_off)
+        r.npairs, r.pair_ours, r.pair_theirs = self.count(self.ours), self.ptr(self.ours), self.ptr(self.theirs)
+        self.r = r
+        self.mem = L.CORRO_MEM_DEVICE if device else L.CORRO_MEM_HOST
+        F, P = r.nframes, r.npairs
+        o = L.StateDecOut()
+        res = {k: self.new(F * w, dt) for k, dt, w in _STATE_FRAME}
+        res["pair_status"] = self.new(P, "uint8")
+        res["pair_ent_off"] = self.new(P + 1, "int64")
+        for k, a in res.items():
+            setattr(o, k, self.ptr(a))
+        self._call(o, 0)
+        for k, _dt, w in _STATE_FRAME:
+            res[k] = res[k][:F * w]
+        res["frame_actor"] = res["frame_actor"].reshape(F, 16)
+        res["pair_status"], res["pair_ent_off"] = res["pair_status"][:P], res["pair_ent_off"][:P + 1]
+        self.head, self.o = res, o
+        self.totals = {k: getattr(o, k) for k in _STATE_TOTALS}
+
+    def _call(self, o, which):
+        if self.device:
+            self.torch.cuda.current_stream().synchronize()
+        L.check(L.lib().corro_decode_states(self.engine._h, C.byref(self.r), self.mem, C.byref(o), which))
+
+    def fill(self):
+        """Pass 1: the entry arrays (sites as the engine knows them now)."""
+        t = self.totals
+        res = dict(self.head)
+        for k, (tot, extra) in _STATE_ENT.items():
+            res[k] = self.new(t[tot] + extra, "int64")
+        res["entry_pair"] = self.new(t["n"], "int32")
+        res["entry_site"] = self.new(t["n"], "int32")
+        res["entry_actor"] = self.new(16 * t["n"], "uint8")
+        for k in tuple(_STATE_ENT) + ("entry_pair", "entry_site", "entry_actor"):
+            setattr(self.o, k, self.ptr(res[k]))
+        self._call(self.o, 1)
+        for k, (tot, extra) in _STATE_ENT.items():
+            res[k] = res[k][:t[tot] + extra]
+        res["entry_pair"], res["entry_site"] = res["entry_pair"][:t["n"]], res["entry_site"][:t["n"]]
+        res["entry_actor"] = res["entry_actor"][:16 * t["n"]].reshape(t["n"], 16)
+        if not self.device:
+            res["entry_site"] = res["entry_site"].view(np.uint32)
+            for k in _STATE_ENT:
+                if k != "our_head":
+                    res[k] = res[k].view(np.uint64)
+        res["nunregistered"] = t["nunregistered"] = self.o.nunregistered   # (as the site table stands now)
+        return res
+
+
+def entries_from_state_frames(engine, buf, frame_off, pairs, device=False):
+    """corro_decode_states, both passes: SyncMessageV1::State frames -> the need diff's entries. `buf` holds
+    the frames back to back, frame f = buf[frame_off[f]:frame_off[f + 1]] with its length prefix; `pairs` is
+    a list (or n x 2 array) of (ours, theirs) frame indices. Host numpy arrays, or with device=True CUDA
+    tensors (buf a CUDA uint8 tensor): then only totals reach the host. Returns the dict of
+    entries_from_states' keys (uint64 arrays, our_head int64; int64 CUDA tensors) plus entry_pair,
+    entry_actor (n x 16), entry_site (0xFFFFFFFF: not registered; -1 in the int32 tensor), pair_status,
+    pair_ent_off, frame_status, frame_actor (nframes x 16), frame_has_ts, frame_ts and nunregistered."""
+    return _StateFrames(engine, buf, frame_off, pairs, device).fill()
+
+
+def requests_from_state_frames(engine, buf, frame_off, sessions, chunk=10, drain=10):
+    """Peer state bytes in, request bytes out, on the device: sessions = [(ours_frame, [theirs_frame, ...]),
+    ...] over the State frames of the CUDA uint8 tensor `buf`. Decodes every (ours, theirs) pair
+    (corro_decode_states), diffs them (corro_compute_needs) and plans the requests (corro_plan_requests)
+    with one group per pair in session order. Actors the engine has not seen are registered: only their
+    distinct ids are read back, and the entries are filled again. Returns plan_requests_device's result
+    plus `groups`, groups[g] = (session number, server number), and `pair_status`."""
+    import torch
+    groups = [(sn, sv) for sn, (_o, servers) in enumerate(sessions) for sv in range(len(servers))]
+    pairs = np.array([(o, t) for o, servers in sessions for t in servers], np.int64).reshape(-1, 2)
+    dec = _StateFrames(engine, buf, frame_off, pairs, True)
+    ent = dec.fill()
+    if ent["nunregistered"]:
+        ids = torch.unique(ent["entry_actor"][ent["entry_site"] == -1], dim=0)
+        engine.register_sites(ids.cpu().numpy().reshape(-1))
+        ent = dec.fill()
+    needs = _needs_device(engine, {k: ent[k] for k in _ENT_KEYS})
+    dev = ent["their_head"].device
+    res = plan_requests_device(engine, needs, ent["entry_site"], ent["pair_ent_off"],
+                               torch.tensor([g[0] for g in groups], dtype=torch.int64, device=dev), chunk, drain)
+    res["groups"], res["pair_status"] = groups, ent["pair_status"]
+    return res
+
+
 def batch_compute_available_needs(engine, pairs):
     """compute_available_needs for many (ours, theirs) pairs in one kernel launch pair."""
     ent, index = entries_from_states(pairs)

@@ -175,6 +175,80 @@ def decode_sync_request(payload):
     return out
 
 
+def encode_sync_state(state):
+    """SyncMessage::V1(SyncMessageV1::State(state)) for a sync.SyncStateV1 (sync.rs:19-30, :79-87): u32 0,
+    u32 0, the 16 id bytes, heads = u32 n + (actor, u64 head)*, need = u32 n + (actor, Vec of (start, end))*,
+    partial_need = u32 n + (actor, u32 m + (version, Vec of (start, end))*)*, last_cleared_ts = u8 0 | u8 1 +
+    u64. A HashMap goes on the wire in iteration order: the dicts' order is kept."""
+    if len(state.actor_id) != 16:
+        raise ValueError("an actor id is 16 bytes")
+    ranges = lambda rs: _u32(len(rs)) + b"".join(_u64(s) + _u64(e) for s, e in rs)
+    out = [_u32(0), _u32(0), bytes(state.actor_id), _u32(len(state.heads))]
+    out += [bytes(a) + _u64(h) for a, h in state.heads.items()]
+    out.append(_u32(len(state.need)))
+    out += [bytes(a) + ranges(rs) for a, rs in state.need.items()]
+    out.append(_u32(len(state.partial_need)))
+    for a, part in state.partial_need.items():
+        out.append(bytes(a) + _u32(len(part)) + b"".join(_u64(v) + ranges(rs) for v, rs in part.items()))
+    out.append(b"\x00" if state.last_cleared_ts is None else b"\x01" + _u64(state.last_cleared_ts))
+    if any(len(a) != 16 for m in (state.heads, state.need, state.partial_need) for a in m):
+        raise ValueError("an actor id is 16 bytes")
+    return b"".join(out)
+
+
+def decode_sync_state(payload):
+    """The inverse of encode_sync_state: a sync.SyncStateV1 with need ranges as lists of (start, end) and
+    the dicts in wire order (a repeated key: the last one wins, as HashMap::insert). last_cleared_ts is
+    default_on_eof: a payload that ends after partial_need decodes to None. Raises ValueError for
+    anything that is not exactly one state."""
+    from . import sync as S
+    pos = 0
+
+    def take(fmt, size):
+        nonlocal pos
+        if pos + size > len(payload):
+            raise ValueError("truncated sync state")
+        v = struct.unpack_from(fmt, payload, pos)[0]
+        pos += size
+        return v
+
+    def actor():
+        return bytes(take("16s", 16))
+
+    def ranges():
+        out = []
+        for _ in range(take("<I", 4)):
+            s = take("<Q", 8)
+            out.append((s, take("<Q", 8)))
+        return out
+
+    if take("<I", 4) != 0 or take("<I", 4) != 0:
+        raise ValueError("not a SyncMessage::V1 State")
+    st = S.SyncStateV1(actor_id=actor())
+    for _ in range(take("<I", 4)):
+        a = actor()
+        st.heads[a] = take("<Q", 8)
+    for _ in range(take("<I", 4)):
+        a = actor()
+        st.need[a] = ranges()
+    for _ in range(take("<I", 4)):
+        a = actor()
+        part = {}
+        for _ in range(take("<I", 4)):
+            v = take("<Q", 8)
+            part[v] = ranges()
+        st.partial_need[a] = part
+    if pos != len(payload):
+        opt = take("B", 1)
+        if opt > 1:
+            raise ValueError(f"Option tag {opt}")
+        if opt:
+            st.last_cleared_ts = take("<Q", 8)
+    if pos != len(payload):
+        raise ValueError("trailing bytes after the sync state")
+    return st
+
+
 def frame(payload):
     """LengthDelimitedCodec frame: u32 big-endian length + payload."""
     return struct.pack(">I", len(payload)) + payload

@@ -468,6 +468,86 @@ int corro_needs_bound(corro_ctx *ctx, const corro_sync_entries *in, int mem, uin
  * (n + 1 outputs), for device-resident need_count / seq_count. */
 int corro_scan_offsets(corro_ctx *ctx, const uint64_t *counts, uint64_t *offsets, uint64_t n);
 
+/* What feeds the need diff, from the wire: SyncMessage::V1(SyncMessageV1::State(SyncStateV1)) frames
+ * (sync.rs:19-30, :79-87) where they lie -> the corro_sync_entries CSR of (ours, theirs) pairs of them.
+ * `buf` / `frame_off`: frame f is buf[frame_off[f], frame_off[f + 1]), its length prefix included (the
+ * caller's codec knows the boundaries; nothing chases length prefixes on the device).
+ *
+ *   u32 BE length | u32 0 (SyncMessage::V1) | u32 0 (SyncMessageV1::State)
+ *   actor_id[16]
+ *   heads:        u32 n | (actor[16], u64 head)*
+ *   need:         u32 n | (actor[16], u32 m, (u64 start, u64 end)*)*
+ *   partial_need: u32 n | (actor[16], u32 m, (u64 version, u32 k, (u64 s, u64 e)*)*)*
+ *   last_cleared_ts (Option<Timestamp>, default_on_eof): nothing | u8 0 | u8 1, u64
+ *
+ * The three maps are HashMaps: their order on the wire is arbitrary. frame_status[f]: 0 ok; 1 a
+ * well-formed message header (SyncMessage::V1, a SyncMessageV1 tag of 1 .. 4) that is not a State
+ * (skipped); 3 an actor twice in one of the three maps or a version twice in one actor's partial map
+ * (the reference's HashMap insert lets the last one win and no encoder produces it: the host codec
+ * handles the frame); CORRO_E_INVALID a frame shorter than its prefix, a prefix that is not the frame's
+ * size - 4, a truncated frame, trailing bytes after the optional timestamp, an option byte other than
+ * 0 / 1 or a message tag above 4; CORRO_E_RANGE a head, need bound or partial version of 2^63 or more
+ * (our_head is an int64 with -1 = None). CORRO_E_INVALID goes before CORRO_E_RANGE and that before 3.
+ * A frame with a status other than 0 emits nothing (its frame_actor is zeros) and affects no other
+ * frame; the call returns 0. Every count on the wire is bounded by the bytes left before it sizes a
+ * loop (a head is 24 bytes, a need actor at least 20, a range 16, a partial actor at least 20, a
+ * partial version at least 12, a seq range 16), and no read leaves the frame.
+ *
+ * A pair names two frames, (ours, theirs); a frame may stand in any number of pairs, on either side.
+ * pair_status[p] is 1 when either frame has a status other than 0 (the pair has no entries), else 0.
+ * The entries are corro_sync_entries' arrays with all their offset arrays (n + 1, ntp + 1, nop + 1
+ * elements), in pair order, then in the wire order of theirs.heads: one per (actor, head) of
+ * theirs.heads with actor != ours.actor_id and head != 0 (sync.rs:133-140); our_head from ours.heads
+ * (-1 when absent); tn_* = theirs.need[actor] in wire order; tp_ver / tps_* = theirs.partial_need[actor]
+ * with the versions ascending (the need diff's canonical order), each version's seq ranges in wire
+ * order; on_* / op_* / ops_* the same from ours. entry_site is the engine's site ordinal of the actor;
+ * one that is not registered gets 0xFFFFFFFF and is NOT registered. nunregistered counts such entries;
+ * it is no size and is set by both passes, so a caller may register the missing ids after either pass
+ * and repeat pass 1.
+ *
+ * Two passes like corro_decode_requests: pass 0 sets the totals and fills the per-frame and per-pair
+ * arrays, the caller allocates, pass 1 decodes again and fills the rest. `mem` covers every array of
+ * both structs; with CORRO_MEM_DEVICE only totals cross PCIe. The call itself fails, before anything is
+ * written, with CORRO_E_INVALID for a frame_off that decreases or passes len, a pair index at or past
+ * nframes (host arrays are screened before any device work), or pass-1 sizes that differ from pass
+ * 0's (sizes no pass 0 returns -- arrays without entries, seq ranges without versions -- are refused
+ * before any device work); CORRO_E_RANGE for 2^31 frames or pairs or more. The
+ * work per frame is linear in its bytes but for the ranking of one actor's partial versions, which is
+ * quadratic in that actor's list. The state is not read; a poisoned context is served. */
+typedef struct {
+    const uint8_t *buf;
+    uint64_t len;
+    uint64_t nframes;
+    const uint64_t *frame_off;             /* nframes + 1 */
+    uint64_t npairs;
+    const uint32_t *pair_ours, *pair_theirs; /* npairs: frame indices */
+} corro_statedec_in;
+
+typedef struct {
+    uint64_t n, ntn, ntp, ntps, non, nop, nops; /* the sizes: pass 0 outputs, pass 1 inputs */
+    uint64_t nunregistered;                /* entries with entry_site 0xFFFFFFFF (both passes) */
+    int32_t *frame_status;                 /* nframes (pass 0) */
+    uint8_t *frame_actor;                  /* 16 * nframes (pass 0): the sender's actor_id */
+    uint8_t *frame_has_ts;                 /* nframes (pass 0): last_cleared_ts is Some */
+    uint64_t *frame_ts;                    /* nframes (pass 0) */
+    uint8_t *pair_status;                  /* npairs (pass 0) */
+    uint64_t *pair_ent_off;                /* npairs + 1 (pass 0): the pair's entries */
+    /* pass 1: corro_sync_entries' arrays */
+    uint64_t *their_head;
+    int64_t *our_head;
+    uint64_t *tn_off, *tn_start, *tn_end;
+    uint64_t *tp_off, *tp_ver;
+    uint64_t *tps_off, *tps_start, *tps_end;
+    uint64_t *on_off, *on_start, *on_end;
+    uint64_t *op_off, *op_ver;
+    uint64_t *ops_off, *ops_start, *ops_end;
+    uint32_t *entry_pair;                  /* n */
+    uint8_t *entry_actor;                  /* 16 * n */
+    uint32_t *entry_site;                  /* n: site ordinal, 0xFFFFFFFF = not registered */
+} corro_statedec_out;
+
+int corro_decode_states(corro_ctx *ctx, const corro_statedec_in *in, int mem, corro_statedec_out *out, int pass);
+
 /* ------------------------------------------------------------------ changeset extraction */
 
 /* Server side of a sync need (handle_need, corro-agent/src/api/peer/mod.rs:371-727): for every
