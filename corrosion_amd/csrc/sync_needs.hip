@@ -10,6 +10,9 @@
 //     else they have partial v -> Partial(v, seqs ∩ ({0..=max end} − their seqs)) if non-empty
 //   Full(our_head+1..=head) if head > our_head, Full(1..=head) if we have no head (sync.rs:229-245)
 // "maximal haves range" is realised by a sweep that jumps over holes, so no set is materialised.
+// A range of ours may be inverted (start > end) in a peer's message, a need range and a seq range
+// alike; overlapping() then yields the have range spanning it and the range is pushed as is
+// (have_spans). Ranges of theirs are never inverted: RangeInclusiveSet::remove asserts start <= end.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -74,14 +77,22 @@ template <class V> struct VerHolesT {
             }
         return hit;
     }
-    // smallest hole start > x (UINT64_MAX if none)
-    __device__ inline uint64_t next_start(uint64_t x) const {
-        uint64_t m = ~0ULL;
+    // smallest hole start > x into m; false if there is none (a flag, not a sentinel value: a hole
+    // may start at UINT64_MAX)
+    __device__ inline bool next_start(uint64_t x, uint64_t &m) const {
+        bool any = false;
+        m = ~0ULL;
         for (uint64_t k = h0; k < h1; k++)
-            if (hs[k] > x && hs[k] < m) m = hs[k];
+            if (hs[k] > x && hs[k] <= m) {
+                m = hs[k];
+                any = true;
+            }
         for (uint64_t k = p0; k < p1; k++)
-            if (pv[k] > x && pv[k] < m) m = pv[k];
-        return m;
+            if (pv[k] > x && pv[k] <= m) {
+                m = pv[k];
+                any = true;
+            }
+        return any;
     }
 };
 
@@ -107,12 +118,16 @@ struct RegHoles {
             }
         return hit;
     }
-    __device__ inline uint64_t next_start(uint64_t x) const {
-        uint64_t m = ~0ULL;
+    __device__ inline bool next_start(uint64_t x, uint64_t &m) const {
+        bool any = false;
+        m = ~0ULL;
 #pragma unroll
         for (int k = 0; k < NEED_RH; k++)
-            if ((uint32_t)k < n && hs[k] > x && hs[k] < m) m = hs[k];
-        return m;
+            if ((uint32_t)k < n && hs[k] > x && hs[k] <= m) {
+                m = hs[k];
+                any = true;
+            }
+        return any;
     }
 };
 
@@ -128,13 +143,26 @@ template <class V> struct SeqHolesT {
             }
         return hit;
     }
-    __device__ inline uint64_t next_start(uint64_t x) const {
-        uint64_t m = ~0ULL;
+    __device__ inline bool next_start(uint64_t x, uint64_t &m) const {
+        bool any = false;
+        m = ~0ULL;
         for (uint64_t k = h0; k < h1; k++)
-            if (hs[k] > x && hs[k] < m) m = hs[k];
-        return m;
+            if (hs[k] > x && hs[k] <= m) {
+                m = hs[k];
+                any = true;
+            }
+        return any;
     }
 };
+
+// An inverted range s > t against the haves (universe − holes): rangemap's overlapping(s..=t)
+// yields every stored range with end >= s and start <= t, i.e. a have range spanning [t, s] (t in no
+// hole, no hole starting in (t, s]); the caller checks [t, s] against the universe.
+template <class H> __device__ inline bool have_spans(const H &holes, uint64_t s, uint64_t t) {
+    uint64_t dummy, ns;
+    if (holes.covering(t, dummy)) return false;
+    return !(holes.next_start(t, ns) && ns <= s);
+}
 
 // Visit maximal pieces of ([lo, hi] ∩ universe[ulo, uhi]) − holes in ascending order.
 template <class H, class F>
@@ -148,8 +176,9 @@ __device__ inline void sweep(const H &holes, uint64_t lo, uint64_t hi, uint64_t 
             x = e + 1;
             continue;
         }
-        const uint64_t ns = holes.next_start(x);
-        const uint64_t pe = (ns == ~0ULL || ns - 1 > top) ? top : ns - 1;
+        uint64_t ns;
+        const bool any = holes.next_start(x, ns);
+        const uint64_t pe = (!any || ns - 1 > top) ? top : ns - 1;
         emit(x, pe);
         if (pe >= top) return;
         x = pe + 1;
@@ -267,12 +296,8 @@ __device__ inline void walk_entry_h(const EntryHdr &h, const InViews<V> &iv, con
     auto our_range = [&](uint64_t s, uint64_t t) {
         if (s > t) {
             // an inverted (empty) range, which no RangeInclusiveSet holds but a peer's message may:
-            // rangemap's overlapping(s..=t) yields every stored range with end >= s and start <= t,
-            // i.e. a have range spanning [t, s], and the reference then pushes Full(s..=t) as is
-            if (t >= 1 && s <= head) {
-                uint64_t dummy;
-                if (!vh.covering(t, dummy) && vh.next_start(t) > s) full(s, t);
-            }
+            // a have range spanning [t, s] overlaps it, and the reference then pushes Full(s..=t) as is
+            if (t >= 1 && s <= head && have_spans(vh, s, t)) full(s, t);
             return;
         }
         sweep(vh, s, t, 1, head, full);
@@ -335,7 +360,14 @@ __device__ inline void walk_entry_h(const EntryHdr &h, const InViews<V> &iv, con
             if (FILL) em.seq(first + cnt, s, t);
             cnt++;
         };
-        for (uint64_t j = q0; j < q1; j++) sweep(sh, iv.opss[j], iv.opse[j], 0, end, piece);
+        for (uint64_t j = q0; j < q1; j++) {
+            const uint64_t s = iv.opss[j], t = iv.opse[j];
+            if (s > t) {  // inverted, as for our need ranges: (s, t) as is under a seq have range
+                if (s <= end && have_spans(sh, s, t)) piece(s, t);
+                continue;
+            }
+            sweep(sh, s, t, 0, end, piece);
+        }
         if (cnt) {
             if (FILL) em.partial(nbase + nn, v, first, cnt);
             nn++;

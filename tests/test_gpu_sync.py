@@ -93,8 +93,10 @@ def _dense_side(rng, nranges, head):
 
 @pytest.mark.parametrize("dense", ["theirs", "ours", "both"])
 def test_sync_lds_caps_exceeded_vs_oracle(dense):
-    """Workgroups whose staged need ranges (> 640 per side) or outputs (> 960 needs) exceed the LDS
-    caps of k_needs take the global-memory path; mixed with normal workgroups in one launch."""
+    """Workgroups whose staged need ranges (> 576 per side, NEEDS_CAP_R) or outputs (> 800 needs,
+    NEEDS_CAP_O) exceed the LDS caps of k_needs take the global-memory path; mixed with normal
+    workgroups in one launch. The heavy workgroups here carry about 3000 ranges and no partials;
+    tests/test_gpu_need_edges.py sits at each cap (also NEEDS_CAP_P 64, NEEDS_CAP_S 160) and one past."""
     rng = np.random.default_rng(11)
     pairs = []
     for i in range(1200):
