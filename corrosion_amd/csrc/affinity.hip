@@ -605,18 +605,13 @@ __global__ void __launch_bounds__(256) k_aff_convert(BatchDev in, const uint8_t 
 }
 
 int arena_reserve(corro_ctx *ctx, uint64_t add);  // engine.hip
-#define AFF_TRY(x)                   \
-    do {                             \
-        if (int rc_ = (x)) return rc_; \
-    } while (0)
-
 // The converted values of the batch (affinity.hip header comment): bd.conv / cv0 / cv1 / cmeta set
 // when some change is converted, left null otherwise.
 int affinity_convert(corro_ctx *ctx, BatchDev &bd) {
     if (!ctx->aff_any || bd.n == 0) return CORRO_OK;
     hipStream_t s = ctx->stream;
     const uint64_t n = bd.n;
-    AFF_TRY(ctx->d_aff_conv.ensure(n));
+    CORRO_TRY(ctx->d_aff_conv.ensure(n));
     unsigned long long *cnt = ctx->d_affflag.as<unsigned long long>();
     CORRO_HIP_TRY(hipMemsetAsync(cnt, 0, 32, s));
     uint8_t *conv = ctx->d_aff_conv.as<uint8_t>();
@@ -635,12 +630,12 @@ int affinity_convert(corro_ctx *ctx, BatchDev &bd) {
                                    "CORRO_AFF_POLICY_PORTABLE (corro_set_affinity_policy)");
     ctx->metrics.aff_sensitive += h[3];  // (counted at staging: a batch that later fails is counted too)
     // 20 bytes per change of the batch: cv0 | cv1 | cmeta
-    AFF_TRY(ctx->d_aff_vals.ensure(n * 20));
+    CORRO_TRY(ctx->d_aff_vals.ensure(n * 20));
     uint64_t *cv0 = ctx->d_aff_vals.as<uint64_t>(), *cv1 = cv0 + n;
     uint32_t *cmeta = (uint32_t *)(cv1 + n);
     uint64_t slot_base = 0;
     if (h[1]) {
-        AFF_TRY(arena_reserve(ctx, h[1] * 24));
+        CORRO_TRY(arena_reserve(ctx, h[1] * 24));
         slot_base = ctx->arena_top;
         ctx->arena_top += h[1] * 24;
     }

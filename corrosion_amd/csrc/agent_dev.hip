@@ -22,6 +22,7 @@
 #include <cstdlib>
 
 #include "internal.h"
+#include "scratch_core.h"
 
 extern "C" uint64_t corro_detail_chunk_changes(const corro_ctx *ctx);  // engine.hip (apply chunk size)
 
@@ -428,7 +429,6 @@ __global__ void __launch_bounds__(AG_T) k_span_fin(const uint64_t *__restrict__ 
     if (__any(gap) && (threadIdx.x & 63) == 0) *info = 1u;  // (a plain store: every writer stores 1)
 }
 
-size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct Field {
     size_t off;   // offsetof(corro_changes, <array>)

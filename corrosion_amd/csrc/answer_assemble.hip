@@ -28,7 +28,7 @@
 //                destination share the misalignment) or two, funnelled; when it spans a piece
 //                boundary, byte reads with one search per piece entered. One 16-byte store per block;
 //                byte stores only at the buffer's two ends
-//   k_as_fold    the error flags: every workgroup of the check stores one partial word, one workgroup
+//   k_flag_fold  (scratch.h) the error flags: every workgroup of the check stores one partial word, one workgroup
 //                folds them (no same-address atomic per wave), and the total
 //                next to them: one read-back
 #include <hip/hip_runtime.h>
@@ -36,6 +36,7 @@
 #include <algorithm>
 
 #include "internal.h"
+#include "scratch.h"
 
 namespace corro {
 int prim_inclusive_sum_u64(void *temp, size_t *temp_bytes, const uint64_t *in, uint64_t *out, uint64_t n, hipStream_t s);
@@ -110,16 +111,7 @@ template <int P> __global__ void k_as_check(AsDev d) {
             if (i == d.benc_nframes) bad |= d.benc_frame_off[i] > d.benc_nbytes;
         }
     }
-    const int any = __syncthreads_or(bad ? 1 : 0);
-    if (threadIdx.x == 0) d.part[blockIdx.x] = any ? 1u : 0u;
-}
-
-// One workgroup: misc[0] |= any partial.
-__global__ void k_as_fold(const uint32_t *part, uint64_t n, unsigned long long *misc) {
-    bool bad = false;
-    for (uint64_t i = threadIdx.x; i < n; i += blockDim.x) bad |= part[i] != 0;
-    const int any = __syncthreads_or(bad ? 1 : 0);
-    if (threadIdx.x == 0 && any) misc[0] = 1;
+    wg_flag(d.part, bad);
 }
 
 // Need t: the lengths and source addresses of its P pieces: P * t the encoded frames, with P = 3 the
@@ -258,34 +250,10 @@ __global__ void __launch_bounds__(256) k_as_copy(AsDev d, uint8_t *buf, uint32_t
     }
 }
 
-size_t al(size_t b) { return ((b + 255) / 256) * 256; }
-
-struct Carver {
-    uint8_t *q = nullptr;
-    template <class T> T *take(size_t count) {
-        uint8_t *r = q;
-        q += al(count * sizeof(T));
-        return reinterpret_cast<T *>(r);
-    }
-};
-
-dim3 grid_for(uint64_t n) { return dim3((uint32_t)((n + 255) / 256)); }
-
 }  // namespace
 }  // namespace corro
 
 using namespace corro;
-
-#define AS_LAUNCH(kernel, count, ...)                                                      \
-    do {                                                                                   \
-        hipLaunchKernelGGL(kernel, grid_for(std::max<uint64_t>(count, 1)), dim3(256), 0, s, __VA_ARGS__); \
-        CORRO_HIP_TRY(hipGetLastError());                                                  \
-    } while (0)
-#define AS_TRY(x)                        \
-    do {                                 \
-        int rc_ = (x);                   \
-        if (rc_ != CORRO_OK) return rc_; \
-    } while (0)
 
 // P pieces per need; bin (P = 3 only): the buffered piece's arrays, in = &bin->base.
 template <int P>
@@ -339,63 +307,51 @@ static int assemble(corro_ctx *ctx, const corro_assemble_in *in, const corro_ass
     const uint64_t ncheck = std::max({F, NP, T, NS ? std::max(NS, EF) : 0, BS ? std::max(BS, BF) : 0}) + 1;
     const uint64_t wg_check = (ncheck + 255) / 256;
     size_t temp = 0;
-    AS_TRY(prim_inclusive_sum_u64(nullptr, &temp, nullptr, nullptr, std::max<uint64_t>(P * T, 1), s));
+    CORRO_TRY(prim_inclusive_sum_u64(nullptr, &temp, nullptr, nullptr, std::max<uint64_t>(P * T, 1), s));
     temp += 256;
-    // (+ 32 behind a staged source buffer: the aligned loads' granules)
-    const size_t stage = host ? al((F + 1) * 8) + al((NP + 1) * 8) + 2 * al(T + 1) + 2 * al((T + 1) * 8) + al((NS + 1) * 8) +
-                                    al((EF + 1) * 8) + al(EB + 32) + al(TB + 32) +
-                                    (P == 3 ? al((T + 1) * 8) + al((BS + 1) * 8) + al((BF + 1) * 8) + al(BB + 32) : 0)
-                              : 0;
-    AS_TRY(ctx->d_reqdec[0].ensure(256 + al(wg_check * 4) + 2 * al(P * T * 8 + 8) + al((P * T + 1) * 8) + al((T + 1) * 8) +
-                                   al((F + 1) * 8) + al(F + 1) + al(temp) + stage));
-    Carver c0{ctx->d_reqdec[0].as<uint8_t>()};
-    d.misc = c0.take<unsigned long long>(32);
-    d.part = c0.take<uint32_t>(wg_check);
-    d.len = c0.take<uint64_t>(P * T + 1);
-    d.psrc = c0.take<uint64_t>(P * T + 1);
-    d.po = c0.take<uint64_t>(P * T + 1);
-    d.need_ans_off = c0.take<uint64_t>(T + 1);
-    d.frame_ans_off = c0.take<uint64_t>(F + 1);
-    d.frame_host = c0.take<uint8_t>(F + 1);
-    void *tmp = c0.take<uint8_t>(temp);
-    if (host) {
-        bool ok = true;
-        auto up = [&](const void *src, size_t b, size_t room) -> const void * {
-            uint8_t *dst = c0.take<uint8_t>(room);
-            if (b && hipMemcpyAsync(dst, src, b, hipMemcpyHostToDevice, s) != hipSuccess) ok = false;
-            return dst;
-        };
-        d.in.frame_pair_off = (const uint64_t *)up(in->frame_pair_off, (F + 1) * 8, (F + 1) * 8);
-        d.in.pair_need_off = (const uint64_t *)up(in->pair_need_off, (NP + 1) * 8, (NP + 1) * 8);
-        d.in.need_keep = (const uint8_t *)up(in->need_keep, T, T + 1);
-        d.in.need_host = (const uint8_t *)up(in->need_host, T, T + 1);
-        d.in.need_span_off = (const uint64_t *)up(in->need_span_off, (T + 1) * 8, (T + 1) * 8);
-        d.in.need_tail_off = (const uint64_t *)up(in->need_tail_off, (T + 1) * 8, (T + 1) * 8);
-        d.in.span_frame_off = (const uint64_t *)up(in->span_frame_off, NS ? (NS + 1) * 8 : 0, (NS + 1) * 8);
-        d.in.enc_frame_off = (const uint64_t *)up(in->enc_frame_off, NS ? (EF + 1) * 8 : 0, (EF + 1) * 8);
-        d.in.enc_buf = (const uint8_t *)up(in->enc_buf, NS ? EB : 0, EB + 32);
-        d.in.tail_buf = (const uint8_t *)up(in->tail_buf, TB, TB + 32);
+    Stager st{s, host};
+    void *tmp = nullptr;
+    CORRO_TRY(carve(ctx->d_reqdec[0], [&](Carver &c) {
+        d.misc = c.take<unsigned long long>(32);
+        d.part = c.take<uint32_t>(wg_check);
+        d.len = c.take<uint64_t>(P * T + 1);
+        d.psrc = c.take<uint64_t>(P * T + 1);
+        d.po = c.take<uint64_t>(P * T + 1);
+        d.need_ans_off = c.take<uint64_t>(T + 1);
+        d.frame_ans_off = c.take<uint64_t>(F + 1);
+        d.frame_host = c.take<uint8_t>(F + 1);
+        tmp = c.take<uint8_t>(temp);
+        // (+ 32 behind a staged source buffer: the aligned loads' granules)
+        d.in.frame_pair_off = c.up(in->frame_pair_off, (F + 1) * 8, (F + 1) * 8);
+        d.in.pair_need_off = c.up(in->pair_need_off, (NP + 1) * 8, (NP + 1) * 8);
+        d.in.need_keep = c.up(in->need_keep, T, T + 1);
+        d.in.need_host = c.up(in->need_host, T, T + 1);
+        d.in.need_span_off = c.up(in->need_span_off, (T + 1) * 8, (T + 1) * 8);
+        d.in.need_tail_off = c.up(in->need_tail_off, (T + 1) * 8, (T + 1) * 8);
+        d.in.span_frame_off = c.up(in->span_frame_off, NS ? (NS + 1) * 8 : 0, (NS + 1) * 8);
+        d.in.enc_frame_off = c.up(in->enc_frame_off, NS ? (EF + 1) * 8 : 0, (EF + 1) * 8);
+        d.in.enc_buf = c.up(in->enc_buf, NS ? EB : 0, EB + 32);
+        d.in.tail_buf = c.up(in->tail_buf, TB, TB + 32);
         if (P == 3) {
-            d.need_bspan_off = (const uint64_t *)up(bin->need_bspan_off, (T + 1) * 8, (T + 1) * 8);
-            d.bspan_frame_off = (const uint64_t *)up(bin->bspan_frame_off, BS ? (BS + 1) * 8 : 0, (BS + 1) * 8);
-            d.benc_frame_off = (const uint64_t *)up(bin->benc_frame_off, BS ? (BF + 1) * 8 : 0, (BF + 1) * 8);
-            d.benc_buf = (const uint8_t *)up(bin->benc_buf, BS ? BB : 0, BB + 32);
+            d.need_bspan_off = c.up(bin->need_bspan_off, (T + 1) * 8, (T + 1) * 8);
+            d.bspan_frame_off = c.up(bin->bspan_frame_off, BS ? (BS + 1) * 8 : 0, (BS + 1) * 8);
+            d.benc_frame_off = c.up(bin->benc_frame_off, BS ? (BF + 1) * 8 : 0, (BF + 1) * 8);
+            d.benc_buf = c.up(bin->benc_buf, BS ? BB : 0, BB + 32);
         }
-        if (!ok) return fail(CORRO_E_DEVICE, "upload of the answer pieces failed");
-    }
+    }, &st));
+    if (!st.ok) return fail(CORRO_E_DEVICE, "upload of the answer pieces failed");
     CORRO_HIP_TRY(hipMemsetAsync(d.misc, 0, 256, s));
     CORRO_HIP_TRY(hipMemsetAsync(d.po, 0, 8, s));
     CORRO_HIP_TRY(hipMemsetAsync(d.frame_host, 0, F + 1, s));
-    AS_LAUNCH(k_as_check<P>, ncheck, d);
-    hipLaunchKernelGGL(k_as_fold, dim3(1), dim3(256), 0, s, (const uint32_t *)d.part, wg_check, d.misc);
-    CORRO_HIP_TRY(hipGetLastError());
+    CORRO_LAUNCH(k_as_check<P>, grid_for(ncheck), d);
+    CORRO_LAUNCH(k_flag_fold, dim3(1), d.part, wg_check, d.misc, fold_totals(0, {}));
     if (T) {
-        AS_LAUNCH(k_as_pieces<P>, T, d);
+        CORRO_LAUNCH(k_as_pieces<P>, grid_for(T), d);
         size_t t = temp;
-        AS_TRY(prim_inclusive_sum_u64(tmp, &t, d.len, d.po + 1, P * T, s));
+        CORRO_TRY(prim_inclusive_sum_u64(tmp, &t, d.len, d.po + 1, P * T, s));
     }
     CORRO_HIP_TRY(hipMemcpyAsync(d.misc + 1, d.po + P * T, 8, hipMemcpyDeviceToDevice, s));
-    if (pass == 0) AS_LAUNCH(k_as_frames<P>, std::max(T, F) + 1, d);
+    if (pass == 0) CORRO_LAUNCH(k_as_frames<P>, grid_for(std::max(T, F) + 1), d);
     unsigned long long misc[2] = {0, 0};
     CORRO_HIP_TRY(hipMemcpyAsync(misc, d.misc, sizeof(misc), hipMemcpyDeviceToHost, s));
     CORRO_HIP_TRY(hipStreamSynchronize(s));
@@ -418,14 +374,12 @@ static int assemble(corro_ctx *ctx, const corro_assemble_in *in, const corro_ass
     if (NB == 0) return CORRO_OK;
     uint8_t *buf = out->buf;
     if (host) {
-        AS_TRY(ctx->d_reqdec[1].ensure(al(NB + 16)));
+        CORRO_TRY(ctx->d_reqdec[1].ensure(NB + 16));
         buf = ctx->d_reqdec[1].as<uint8_t>();
     }
     const uint32_t lead = (uint32_t)(reinterpret_cast<uintptr_t>(buf) & 15);
     const uint64_t nblocks = (lead + NB + 15) / 16;
-    hipLaunchKernelGGL(k_as_copy, dim3((uint32_t)((nblocks + AS_TILE - 1) / AS_TILE)), dim3(256), 0, s, d, buf, lead, NB,
-                       nblocks, P * T + 1);
-    CORRO_HIP_TRY(hipGetLastError());
+    CORRO_LAUNCH(k_as_copy, dim3((uint32_t)((nblocks + AS_TILE - 1) / AS_TILE)), d, buf, lead, NB, nblocks, P * T + 1);
     if (host) CORRO_HIP_TRY(hipMemcpyAsync(out->buf, buf, NB, hipMemcpyDeviceToHost, s));
     CORRO_HIP_TRY(hipStreamSynchronize(s));
     return CORRO_OK;

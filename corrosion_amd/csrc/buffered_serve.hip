@@ -22,7 +22,7 @@
 //   k_bs_gather  driven from the output: one lane per output row finds its piece by binary search (the
 //                last piece that starts at or before it) and copies the twelve columns, so consecutive
 //                lanes read consecutive pool rows and write consecutive output rows
-//   k_bs_fold    the error flags, one partial word per workgroup of the check folded by one workgroup
+//   k_flag_fold  (scratch.h) the error flags, one partial word per workgroup of the check folded by one workgroup
 //                (no same-address atomic per wave)
 #include <hip/hip_runtime.h>
 
@@ -30,6 +30,7 @@
 
 #include "agent_dev.h"
 #include "internal.h"
+#include "scratch.h"
 
 namespace corro {
 int prim_inclusive_sum_u64(void *temp, size_t *temp_bytes, const uint64_t *in, uint64_t *out, uint64_t n, hipStream_t s);
@@ -101,16 +102,7 @@ __global__ void k_bs_check(BsDev d) {
         bad |= po > d.top || n > d.top - po;
         if (i + 1 < NG && same_slice(in.seg_off, NV, i)) bad |= (uint64_t)in.seg_seq0[i] + n > in.seg_seq0[i + 1];
     }
-    const int any = __syncthreads_or(bad ? 1 : 0);
-    if (threadIdx.x == 0) d.part[blockIdx.x] = any ? 1u : 0u;
-}
-
-// One workgroup: misc[0] |= any partial.
-__global__ void k_bs_fold(const uint32_t *part, uint64_t n, unsigned long long *misc) {
-    bool bad = false;
-    for (uint64_t i = threadIdx.x; i < n; i += blockDim.x) bad |= part[i] != 0;
-    const int any = __syncthreads_or(bad ? 1 : 0);
-    if (threadIdx.x == 0 && any) misc[0] = 1;
+    wg_flag(d.part, bad);
 }
 
 // One need's walk. FILL = false: the counts; FILL = true: the spans at so (at most sroom of them), the
@@ -235,34 +227,10 @@ __global__ void k_bs_gather(BsDev d, uint64_t nrows, uint64_t npieces) {
     o.val_len[r] = p.val_len[i];
 }
 
-size_t al(size_t b) { return ((b + 255) / 256) * 256; }
-
-struct Carver {
-    uint8_t *q = nullptr;
-    template <class T> T *take(size_t count) {
-        uint8_t *r = q;
-        q += al(count * sizeof(T));
-        return reinterpret_cast<T *>(r);
-    }
-};
-
-dim3 grid_for(uint64_t n) { return dim3((uint32_t)((n + 255) / 256)); }
-
 }  // namespace
 }  // namespace corro
 
 using namespace corro;
-
-#define BS_LAUNCH(kernel, count, ...)                                                      \
-    do {                                                                                   \
-        hipLaunchKernelGGL(kernel, grid_for(std::max<uint64_t>(count, 1)), dim3(256), 0, s, __VA_ARGS__); \
-        CORRO_HIP_TRY(hipGetLastError());                                                  \
-    } while (0)
-#define BS_TRY(x)                        \
-    do {                                 \
-        int rc_ = (x);                   \
-        if (rc_ != CORRO_OK) return rc_; \
-    } while (0)
 
 extern "C" int corro_buffered_spans(corro_ctx *ctx, corro_bookie *bk, const corro_bufspans_in *in, int mem,
                                     corro_bufspans_out *out, int pass) {
@@ -315,34 +283,34 @@ extern "C" int corro_buffered_spans(corro_ctx *ctx, corro_bookie *bk, const corr
     const uint64_t ncheck = std::max({T, E, (uint64_t)S, NV, NSEG}) + 1;
     const uint64_t wg_check = (ncheck + 255) / 256;
     size_t temp = 0;
-    BS_TRY(prim_inclusive_sum_u64(nullptr, &temp, nullptr, nullptr, std::max<uint64_t>(T, 1), s));
+    CORRO_TRY(prim_inclusive_sum_u64(nullptr, &temp, nullptr, nullptr, std::max<uint64_t>(T, 1), s));
     temp += 256;
-    BS_TRY(ctx->d_reqdec[0].ensure(256 + al(wg_check * 4) + 6 * al((T + 1) * 8) + al(temp)));
-    Carver c0{ctx->d_reqdec[0].as<uint8_t>()};
-    d.misc = c0.take<unsigned long long>(32);
-    d.part = c0.take<uint32_t>(wg_check);
-    d.cnt_s = c0.take<uint64_t>(T + 1);
-    d.cnt_r = c0.take<uint64_t>(T + 1);
-    d.cnt_p = c0.take<uint64_t>(T + 1);
-    d.off_s = c0.take<uint64_t>(T + 1);
-    d.off_r = c0.take<uint64_t>(T + 1);
-    d.off_p = c0.take<uint64_t>(T + 1);
-    void *tmp = c0.take<uint8_t>(temp);
+    void *tmp = nullptr;
+    CORRO_TRY(carve(ctx->d_reqdec[0], [&](Carver &c) {
+        d.misc = c.take<unsigned long long>(32);
+        d.part = c.take<uint32_t>(wg_check);
+        d.cnt_s = c.take<uint64_t>(T + 1);
+        d.cnt_r = c.take<uint64_t>(T + 1);
+        d.cnt_p = c.take<uint64_t>(T + 1);
+        d.off_s = c.take<uint64_t>(T + 1);
+        d.off_r = c.take<uint64_t>(T + 1);
+        d.off_p = c.take<uint64_t>(T + 1);
+        tmp = c.take<uint8_t>(temp);
+    }));
     CORRO_HIP_TRY(hipMemsetAsync(d.misc, 0, 256, s));
     CORRO_HIP_TRY(hipMemsetAsync(d.off_s, 0, 8, s));
     CORRO_HIP_TRY(hipMemsetAsync(d.off_r, 0, 8, s));
     CORRO_HIP_TRY(hipMemsetAsync(d.off_p, 0, 8, s));
-    BS_LAUNCH(k_bs_check, ncheck, d);
-    hipLaunchKernelGGL(k_bs_fold, dim3(1), dim3(256), 0, s, (const uint32_t *)d.part, wg_check, d.misc);
-    CORRO_HIP_TRY(hipGetLastError());
+    CORRO_LAUNCH(k_bs_check, grid_for(ncheck), d);
+    CORRO_LAUNCH(k_flag_fold, dim3(1), d.part, wg_check, d.misc, fold_totals(0, {}));
     if (T) {
-        BS_LAUNCH(k_bs_count, T, d);
+        CORRO_LAUNCH(k_bs_count, grid_for(T), d);
         size_t t = temp;
-        BS_TRY(prim_inclusive_sum_u64(tmp, &t, d.cnt_s, d.off_s + 1, T, s));
+        CORRO_TRY(prim_inclusive_sum_u64(tmp, &t, d.cnt_s, d.off_s + 1, T, s));
         t = temp;
-        BS_TRY(prim_inclusive_sum_u64(tmp, &t, d.cnt_r, d.off_r + 1, T, s));
+        CORRO_TRY(prim_inclusive_sum_u64(tmp, &t, d.cnt_r, d.off_r + 1, T, s));
         t = temp;
-        BS_TRY(prim_inclusive_sum_u64(tmp, &t, d.cnt_p, d.off_p + 1, T, s));
+        CORRO_TRY(prim_inclusive_sum_u64(tmp, &t, d.cnt_p, d.off_p + 1, T, s));
     }
     CORRO_HIP_TRY(hipMemcpyAsync(d.misc + 1, d.off_s + T, 8, hipMemcpyDeviceToDevice, s));
     CORRO_HIP_TRY(hipMemcpyAsync(d.misc + 2, d.off_r + T, 8, hipMemcpyDeviceToDevice, s));
@@ -365,13 +333,13 @@ extern "C" int corro_buffered_spans(corro_ctx *ctx, corro_bookie *bk, const corr
     if (misc[1] != N || misc[2] != R) return fail(CORRO_E_INVALID, "sizes differ from pass 0");
     if (N == 0) return CORRO_OK;
     const uint64_t NP = misc[3];
-    BS_TRY(ctx->d_reqdec[1].ensure(2 * al((NP + 1) * 8)));
-    Carver c1{ctx->d_reqdec[1].as<uint8_t>()};
-    d.pdst = c1.take<uint64_t>(NP + 1);
-    d.psrc = c1.take<uint64_t>(NP + 1);
+    CORRO_TRY(carve(ctx->d_reqdec[1], [&](Carver &c) {
+        d.pdst = c.take<uint64_t>(NP + 1);
+        d.psrc = c.take<uint64_t>(NP + 1);
+    }));
     d.out = *out;
-    BS_LAUNCH(k_bs_fill, T, d);
-    if (R && NP) BS_LAUNCH(k_bs_gather, R, d, R, NP);
+    CORRO_LAUNCH(k_bs_fill, grid_for(std::max<uint64_t>(T, 1)), d);
+    if (R && NP) CORRO_LAUNCH(k_bs_gather, grid_for(R), d, R, NP);
     CORRO_HIP_TRY(hipStreamSynchronize(s));
     return CORRO_OK;
 }

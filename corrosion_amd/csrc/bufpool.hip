@@ -19,6 +19,7 @@
 
 #include "agent_dev.h"
 #include "internal.h"
+#include "scratch_core.h"
 
 namespace corro {
 
@@ -32,7 +33,6 @@ namespace {
 
 constexpr int BP_T = 256;
 
-size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 dim3 bp_wave_grid(uint64_t n) { return dim3((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + 3) / 4, 16384))); }
 

@@ -51,12 +51,6 @@ void DevBuf::release() {
 
 using namespace corro;
 
-#define TRY(x)                       \
-    do {                             \
-        int rc_ = (x);               \
-        if (rc_ != CORRO_OK) return rc_; \
-    } while (0)
-
 namespace corro {
 int ovf_sort_pairs(void *temp, size_t *temp_bytes, const uint64_t *ki, uint64_t *ko, const uint32_t *vi,
                    uint32_t *vo, uint32_t n, uint32_t end_bit, hipStream_t s);
@@ -94,7 +88,7 @@ static int run_overflow(corro_ctx *ctx, MergeArgs &a, uint64_t novf, uint64_t nb
     uint32_t *const hw = ctx->h_ovf + 8ULL * B;  // (32 readback words; hw + 8: the plan's totals, 8-B aligned)
     // the plan (k_ovf_plan): bucket offsets and row-table slices on the device, totals back
     if (novf > (uint64_t)PLAN_T * PLAN_PER) return fail(CORRO_E_RANGE, "internal: more oversized buckets than k_ovf_plan takes");
-    TRY(ctx->d_ovf_plan.ensure((2ULL * B + 2) * 4 + 16 * 8 + 256));
+    CORRO_TRY(ctx->d_ovf_plan.ensure((2ULL * B + 2) * 4 + 16 * 8 + 256));
     uint32_t *const p_koff = ctx->d_ovf_plan.as<uint32_t>(), *const p_soff = p_koff + B + 1;
     unsigned long long *const p_tot = (unsigned long long *)(((uintptr_t)(p_soff + B) + 15) & ~(uintptr_t)15);
     unsigned long long *const hq = (unsigned long long *)(hw + 8);  // (pinned: tot[0..4])
@@ -183,12 +177,12 @@ static int run_overflow(corro_ctx *ctx, MergeArgs &a, uint64_t novf, uint64_t nb
             temp = ctx->ovf_temp;  // (rocPRIM's temp sizes grow with n; the 64-bit sort bounds the others)
         } else if (pass == 0) {
             size_t t0 = 0, t1 = 0, t2 = 0, t3 = 0;
-            TRY(ovf_sort_pairs(nullptr, &t0, nullptr, nullptr, nullptr, nullptr, d.K, 64, s));
-            TRY(ovf_sort_pairs(nullptr, &t1, nullptr, nullptr, nullptr, nullptr, d.K, ckey_bits, s));
-            TRY(ovf_scans(nullptr, &t2, d, 0, s));
-            TRY(prim_inclusive_scan_u32(nullptr, &t3, nullptr, nullptr, d.K, s));
+            CORRO_TRY(ovf_sort_pairs(nullptr, &t0, nullptr, nullptr, nullptr, nullptr, d.K, 64, s));
+            CORRO_TRY(ovf_sort_pairs(nullptr, &t1, nullptr, nullptr, nullptr, nullptr, d.K, ckey_bits, s));
+            CORRO_TRY(ovf_scans(nullptr, &t2, d, 0, s));
+            CORRO_TRY(prim_inclusive_scan_u32(nullptr, &t3, nullptr, nullptr, d.K, s));
             size_t t4 = 0;
-            TRY(ovf_scan_tiles(nullptr, &t4, d, nullptr, nullptr, (uint32_t)((K + CS_TILE - 1) / CS_TILE), s));
+            CORRO_TRY(ovf_scan_tiles(nullptr, &t4, d, nullptr, nullptr, (uint32_t)((K + CS_TILE - 1) / CS_TILE), s));
             temp = std::max(std::max(std::max(t0, t1), std::max(t2, t3)), t4);
             ctx->ovf_temp_k = K;
             ctx->ovf_temp = temp;
@@ -199,7 +193,7 @@ static int run_overflow(corro_ctx *ctx, MergeArgs &a, uint64_t novf, uint64_t nb
         cs_first = (uint32_t *)take(nt * 4ULL);
         d_temp = take(temp);
         if (pass == 0) {
-            TRY(ctx->d_ovf_sort.ensure(bytes + 256));
+            CORRO_TRY(ctx->d_ovf_sort.ensure(bytes + 256));
             base = ctx->d_ovf_sort.as<uint8_t>();
         }
     }
@@ -231,7 +225,7 @@ static int run_overflow(corro_ctx *ctx, MergeArgs &a, uint64_t novf, uint64_t nb
         // area, or one an apply left before its walk (an error return), is cleared here
         void *const was = ctx->d_ovf_sum.p;
         const size_t was_bytes = ctx->d_ovf_sum.bytes;  // (a regrown area may come back at the same address)
-        TRY(ctx->d_ovf_sum.ensure(Kb * sizeof(OvfSum) + 256));
+        CORRO_TRY(ctx->d_ovf_sum.ensure(Kb * sizeof(OvfSum) + 256));
         if (ctx->d_ovf_sum.p != was || ctx->d_ovf_sum.bytes != was_bytes || ctx->ovf_sum_dirty)
             CORRO_HIP_TRY(hipMemsetAsync(ctx->d_ovf_sum.p, 0, ctx->d_ovf_sum.bytes, s));
         ctx->ovf_sum_dirty = true;  // (until this apply's walk has run)
@@ -246,9 +240,9 @@ static int run_overflow(corro_ctx *ctx, MergeArgs &a, uint64_t novf, uint64_t nb
         hipLaunchKernelGGL(k_ovf_loadsum, dim3((uint32_t)((Kb + RS_CHUNK - 1) / RS_CHUNK)), dim3(RS_T), 0, s, a, d);
     else
         hipLaunchKernelGGL(k_ovf_loadhash, gridb, blk, 0, s, a, d);
-    TRY(launched());
+    CORRO_TRY(launched());
     // dense row ids: the row count sizes the sort's key
-    TRY(prim_inclusive_scan_u32(d_temp, &temp, d.recf, d.epc, d.Kb, s));
+    CORRO_TRY(prim_inclusive_scan_u32(d_temp, &temp, d.recf, d.epc, d.Kb, s));
     CORRO_HIP_TRY(hipMemcpyAsync(&hw[0], d.epc + (Kb - 1), 4, hipMemcpyDeviceToHost, s));
     hp("enq2");
     CORRO_HIP_TRY(hipStreamSynchronize(s));
@@ -259,7 +253,7 @@ static int run_overflow(corro_ctx *ctx, MergeArgs &a, uint64_t novf, uint64_t nb
     if (d.fuse) {  // (summaries by owner record: the per-row block holds the counters)
         d.nkeep = (uint32_t *)rowblk;
         CORRO_HIP_TRY(hipMemsetAsync(d.nkeep, 0, 16, s));
-        TRY(ctx->d_ovf_rcl.ensure((uint64_t)nrows * 4 * 7 + 256));
+        CORRO_TRY(ctx->d_ovf_rcl.ensure((uint64_t)nrows * 4 * 7 + 256));
         d.rsum = ctx->d_ovf_rcl.as<uint64_t>();
         d.rowE = reinterpret_cast<uint32_t *>(d.rsum + nrows);
         d.rlist = d.rowE + nrows;
@@ -274,7 +268,7 @@ static int run_overflow(corro_ctx *ctx, MergeArgs &a, uint64_t novf, uint64_t nb
         if (d.reduce) CORRO_HIP_TRY(hipMemsetAsync(blk, 0, 12ULL * nrows + 8, s));
     }
     if (d.rimp) {  // causal-length slots (free = ~0) and their first records
-        TRY(ctx->d_ovf_rcl.ensure((uint64_t)nrows * OVF_NCL * 12 + 256));
+        CORRO_TRY(ctx->d_ovf_rcl.ensure((uint64_t)nrows * OVF_NCL * 12 + 256));
         d.rcl = ctx->d_ovf_rcl.as<uint64_t>();
         d.rclr = reinterpret_cast<uint32_t *>(d.rcl + (uint64_t)nrows * OVF_NCL);
         CORRO_HIP_TRY(hipMemsetAsync(d.rcl, 0xFF, (uint64_t)nrows * OVF_NCL * 8, s));
@@ -288,8 +282,8 @@ static int run_overflow(corro_ctx *ctx, MergeArgs &a, uint64_t novf, uint64_t nb
         hipLaunchKernelGGL(d.rimp ? k_ovf_lookup<true> : k_ovf_lookup<false>, dim3((uint32_t)((Kb + RS_CHUNK - 1) / RS_CHUNK)),
                            dim3(RS_T), 0, s, a, d);
     if (split) hipLaunchKernelGGL(k_ovf_rlook, grid_for(nrows), blk, 0, s, a, d);
-    TRY(launched());
-    TRY(prim_inclusive_scan_u32(d_temp, &temp, d.rprior, d.rpoff, nrows, s));
+    CORRO_TRY(launched());
+    CORRO_TRY(prim_inclusive_scan_u32(d_temp, &temp, d.rprior, d.rpoff, nrows, s));
     CORRO_HIP_TRY(hipMemcpyAsync(&hw[0], d.rpoff + (nrows - 1), 4, hipMemcpyDeviceToHost, s));
     hipLaunchKernelGGL(k_ovf_room, dim3(1), dim3(PLAN_T), 0, s, ctx->d_ovf_list.as<uint32_t>(), ctx->d_used.as<uint32_t>(),
                        d.bnew, d.bnrec, (uint32_t)novf, p_tot);
@@ -306,8 +300,8 @@ static int run_overflow(corro_ctx *ctx, MergeArgs &a, uint64_t novf, uint64_t nb
     const uint64_t need_heap = hq[4], want = hq[3];  // (k_ovf_room: the largest fill asked of a region)
     uint32_t need_log2S = ctx->log2S;
     while (want > ((7ULL << need_log2S) >> 3)) need_log2S++;
-    if (need_log2S != ctx->log2S) TRY(grow_regions(ctx, need_log2S));
-    if (top + need_heap > ctx->heap_cap) TRY(grow_heap(ctx, top + need_heap));
+    if (need_log2S != ctx->log2S) CORRO_TRY(grow_regions(ctx, need_log2S));
+    if (top + need_heap > ctx->heap_cap) CORRO_TRY(grow_heap(ctx, top + need_heap));
     a.rs = row_store(ctx);
     d.K = (uint32_t)(Kb + P);
     uint32_t rbits = 1;
@@ -321,13 +315,13 @@ static int run_overflow(corro_ctx *ctx, MergeArgs &a, uint64_t novf, uint64_t nb
                 (unsigned long long)novf, (unsigned long long)Kb, P, nrows, key_bits, rbits, ckey_bits);
     hp("room");
     hipLaunchKernelGGL(k_ovf_pload, grid_for(nrows), blk, 0, s, a, d);
-    TRY(launched());
+    CORRO_TRY(launched());
     if (d.reduce) {
         // rows reduced to their last epoch's records (k_ovf_lookup's comment); the rest sort as before
         const uint32_t kcap = d.K;
         hipLaunchKernelGGL(d.fuse ? k_ovf_keep<true> : k_ovf_keep<false>, dim3((d.K + KEEP_CHUNK - 1) / KEEP_CHUNK),
                            dim3(KEEP_T), 0, s, a, d, kcap);
-        TRY(launched());
+        CORRO_TRY(launched());
         CORRO_HIP_TRY(hipMemcpyAsync(&hw[4], d.nkeep, 8, hipMemcpyDeviceToHost, s));
         hp("enq4");
         CORRO_HIP_TRY(hipStreamSynchronize(s));
@@ -342,21 +336,21 @@ static int run_overflow(corro_ctx *ctx, MergeArgs &a, uint64_t novf, uint64_t nb
             // fused form: the reduced rows' cells -- sorted by (owner record, cid), each cell's winner by the
             // argmax scan with the position as the last tie-break -- before the kept records' sort
             // reuses key_s / val_s / qkey / cbest
-            TRY(ovf_sort_pairs(d_temp, &temp, d.ckey + (kcap - nc), d.key_s, d.cval + (kcap - nc), d.val_s, nc,
+            CORRO_TRY(ovf_sort_pairs(d_temp, &temp, d.ckey + (kcap - nc), d.key_s, d.cval + (kcap - nc), d.val_s, nc,
                                d.obits + cid_bits, s));
             const dim3 rgrid = grid_for(nc);
             hipLaunchKernelGGL(k_ovf_rgather, rgrid, blk, 0, s, a, d, nc, d.pb);
-            TRY(launched());
+            CORRO_TRY(launched());
             OvfDev dd = d;
             dd.ckey_s = d.key_s;
             dd.K = nc;
             dd.qpos = d.pb;
             const uint32_t ntc = (nc + CS_TILE - 1) / CS_TILE;  // <= nt
             hipLaunchKernelGGL(k_cscan_tile<true>, dim3(ntc), dim3(CS_T), 0, s, dd, cs_agg, cs_first);
-            TRY(launched());
-            TRY(ovf_scan_tiles(d_temp, &temp, dd, cs_agg, cs_incl, ntc, s));
+            CORRO_TRY(launched());
+            CORRO_TRY(ovf_scan_tiles(d_temp, &temp, dd, cs_agg, cs_incl, ntc, s));
             hipLaunchKernelGGL(k_cscan_fix<true>, dim3(ntc), dim3(CS_T), 0, s, dd, cs_incl, cs_first);
-            TRY(launched());
+            CORRO_TRY(launched());
         }
         // the reduced rows written now (their sentinels and slots, then their cells, one lane per cell),
         // while the cell sort's results are in key_s / val_s / cbest; the other rows' pipeline below
@@ -365,70 +359,70 @@ static int run_overflow(corro_ctx *ctx, MergeArgs &a, uint64_t novf, uint64_t nb
             void (*const walk1)(MergeArgs, OvfDev) = ctx->max_stride <= WALK_MAXC ? k_ovf_walk<true, 1> : k_ovf_walk<false, 1>;
             hipLaunchKernelGGL(walk1, grid_for(nrows), blk, 0, s, a, d);
             if (nc) hipLaunchKernelGGL(k_ovf_rcells, grid_for(nc), blk, 0, s, a, d, nc);
-            TRY(launched());
+            CORRO_TRY(launched());
         }
         if (ndc) {
             // dropped candidates (impact form): sorted by (row, slot, cid, position), running argmax by
             // group with the candidate scan's kernels, then their flags -- all before the kept records'
             // sort reuses key_s / val_s / key / qkey / cbest
             const uint32_t dbits = kbits + 3 + cid_bits + pbits;
-            TRY(ovf_sort_pairs(d_temp, &temp, d.ckey + (kcap - ndc), d.key_s, d.cval + (kcap - ndc), d.val_s, ndc, dbits, s));
+            CORRO_TRY(ovf_sort_pairs(d_temp, &temp, d.ckey + (kcap - ndc), d.key_s, d.cval + (kcap - ndc), d.val_s, ndc, dbits, s));
             const dim3 dgrid = grid_for(ndc);
             hipLaunchKernelGGL(k_ovf_dgather, dgrid, blk, 0, s, a, d, ndc, d.key_s, d.val_s, d.key, d.qkey);
-            TRY(launched());
+            CORRO_TRY(launched());
             OvfDev dd = d;  // the scan reads (ckey_s: group keys, qkey: cell keys, K, cbest)
             dd.ckey_s = d.key;
             dd.K = ndc;
             const uint32_t ntc = (ndc + CS_TILE - 1) / CS_TILE;  // <= nt
             hipLaunchKernelGGL(k_cscan_tile<false>, dim3(ntc), dim3(CS_T), 0, s, dd, cs_agg, cs_first);
-            TRY(launched());
-            TRY(ovf_scan_tiles(d_temp, &temp, dd, cs_agg, cs_incl, ntc, s));
+            CORRO_TRY(launched());
+            CORRO_TRY(ovf_scan_tiles(d_temp, &temp, dd, cs_agg, cs_incl, ntc, s));
             hipLaunchKernelGGL(k_cscan_fix<false>, dim3(ntc), dim3(CS_T), 0, s, dd, cs_incl, cs_first);
             hipLaunchKernelGGL(k_ovf_dimp, dgrid, blk, 0, s, a, d, ndc, d.key, d.val_s, d.qkey, d.cbest);
-            TRY(launched());
+            CORRO_TRY(launched());
         }
         d.K = kept;
-        if (kept) TRY(ovf_sort_pairs(d_temp, &temp, d.ckey, d.key_s, d.cval, d.val_s, d.K, key_bits, s));
+        if (kept) CORRO_TRY(ovf_sort_pairs(d_temp, &temp, d.ckey, d.key_s, d.cval, d.val_s, d.K, key_bits, s));
     } else {
-        TRY(ovf_sort_pairs(d_temp, &temp, d.key, d.key_s, d.val, d.val_s, d.K, key_bits, s));
+        CORRO_TRY(ovf_sort_pairs(d_temp, &temp, d.key, d.key_s, d.val, d.val_s, d.K, key_bits, s));
     }
     d.ncand = 0;
     if (d.K) {  // (fused form: none when every row reduced)
     const dim3 grid = grid_for(d.K);
     hipLaunchKernelGGL(k_ovf_gather, grid, blk, 0, s, d);
-    TRY(launched());
-    TRY(ovf_scans(d_temp, &temp, d, 0, s));
+    CORRO_TRY(launched());
+    CORRO_TRY(ovf_scans(d_temp, &temp, d, 0, s));
     hipLaunchKernelGGL(k_ovf_classify, grid, blk, 0, s, a, d);
-    TRY(launched());
-    TRY(ovf_scans(d_temp, &temp, d, 1, s));
+    CORRO_TRY(launched());
+    CORRO_TRY(ovf_scans(d_temp, &temp, d, 1, s));
     hipLaunchKernelGGL(k_ovf_epochs, grid, blk, 0, s, d);
     hipLaunchKernelGGL(k_ovf_ckeys, grid, blk, 0, s, d);
-    TRY(launched());
+    CORRO_TRY(launched());
     // only the candidates are sorted (a minority of the records): compact them first
-    TRY(prim_inclusive_scan_u32(d_temp, &temp, d.slots, d.slots + d.K, d.K, s));
+    CORRO_TRY(prim_inclusive_scan_u32(d_temp, &temp, d.slots, d.slots + d.K, d.K, s));
     CORRO_HIP_TRY(hipMemcpyAsync(&hw[5], d.slots + d.K + (d.K - 1), 4, hipMemcpyDeviceToHost, s));
     hp("enq5");
     CORRO_HIP_TRY(hipStreamSynchronize(s));
     hp("wait5");
     const uint32_t ncand = hw[5];
     hipLaunchKernelGGL(k_ovf_ccompact, grid, blk, 0, s, d);
-    TRY(launched());
-    if (ncand) TRY(ovf_sort_pairs(d_temp, &temp, d.key, d.ckey_s, d.val, d.cval_s, ncand, ckey_bits, s));
+    CORRO_TRY(launched());
+    if (ncand) CORRO_TRY(ovf_sort_pairs(d_temp, &temp, d.key, d.ckey_s, d.val, d.cval_s, ncand, ckey_bits, s));
     if (ncand < d.K) CORRO_HIP_TRY(hipMemsetAsync(d.ckey_s + ncand, 0xFF, (d.K - ncand) * 8ULL, s));
     if (dbg) fprintf(stderr, "[corro ovf] candidates %u\n", ncand);
     d.ncand = ncand;
     const dim3 cgrid = grid_for(ncand);
     hipLaunchKernelGGL(k_ovf_cgather, cgrid, blk, 0, s, a, d);
-    TRY(launched());
+    CORRO_TRY(launched());
     if (ncand) {
         const uint32_t ntc = (ncand + CS_TILE - 1) / CS_TILE;  // <= nt
         hipLaunchKernelGGL(k_cscan_tile<false>, dim3(ntc), dim3(CS_T), 0, s, d, cs_agg, cs_first);
-        TRY(launched());
-        TRY(ovf_scan_tiles(d_temp, &temp, d, cs_agg, cs_incl, ntc, s));
+        CORRO_TRY(launched());
+        CORRO_TRY(ovf_scan_tiles(d_temp, &temp, d, cs_agg, cs_incl, ntc, s));
         hipLaunchKernelGGL(k_cscan_fix<false>, dim3(ntc), dim3(CS_T), 0, s, d, cs_incl, cs_first);
     }
-    TRY(launched());
-    if (ncand && a.impact) TRY(ovf_scans(d_temp, &temp, d, 2, s));  // (group starts: impacts only)
+    CORRO_TRY(launched());
+    if (ncand && a.impact) CORRO_TRY(ovf_scans(d_temp, &temp, d, 2, s));  // (group starts: impacts only)
     hipLaunchKernelGGL(k_ovf_link, cgrid, blk, 0, s, d);
     }
     // carried cells in registers when no table has WALK_MAXC or more columns (cids 1..ncols)
@@ -443,7 +437,7 @@ static int run_overflow(corro_ctx *ctx, MergeArgs &a, uint64_t novf, uint64_t nb
     }
     if (a.impact && d.ncand) hipLaunchKernelGGL(k_ovf_impacts, grid_for(d.ncand), blk, 0, s, a, d);
     hipLaunchKernelGGL(k_ovf_finish, grid_for(novf), blk, 0, s, a, d);
-    TRY(launched());
+    CORRO_TRY(launched());
     hp("enq6");
     if (hostprof) fprintf(stderr, "[corro ovf host us]%s\n", hp_line.c_str());
     if (prof) (void)hipEventRecord(ctx->ev[7], s);
@@ -505,12 +499,12 @@ static int store_alloc(corro_ctx *ctx, uint64_t capacity_hint) {
     // (region entries are named by 32-bit indices: B << log2S stays <= 2^31)
     while (((uint64_t)B << lg) < 2 * rows && lg < 20 && ((uint64_t)B << (lg + 1)) <= (1ULL << 31)) lg++;
     ctx->log2S = lg;
-    TRY(ctx->d_ent.ensure(((size_t)B << lg) * sizeof(RowEnt)));
-    TRY(ctx->d_used.ensure(B * 4ULL));
-    TRY(ctx->d_gen.ensure(B * 4ULL));
-    TRY(ctx->d_heap_top.ensure(8));
+    CORRO_TRY(ctx->d_ent.ensure(((size_t)B << lg) * sizeof(RowEnt)));
+    CORRO_TRY(ctx->d_used.ensure(B * 4ULL));
+    CORRO_TRY(ctx->d_gen.ensure(B * 4ULL));
+    CORRO_TRY(ctx->d_heap_top.ensure(8));
     ctx->heap_cap = std::min<uint64_t>(1ULL << 31, std::max<uint64_t>(1ULL << 16, capacity_hint / 2));
-    TRY(ctx->d_heap.ensure(ctx->heap_cap * sizeof(Rec)));
+    CORRO_TRY(ctx->d_heap.ensure(ctx->heap_cap * sizeof(Rec)));
     return CORRO_OK;
 }
 
@@ -560,7 +554,7 @@ int arena_reserve(corro_ctx *ctx, uint64_t add) {
     if (need > ARENA_MAX) return fail(CORRO_E_RANGE, "value arena would exceed 2^40 bytes");
     if (need <= ctx->d_arena.bytes && ctx->d_arena.p) return CORRO_OK;
     DevBuf nb;
-    TRY(nb.ensure(std::max<uint64_t>(need + (need >> 1), 1ULL << 20)));
+    CORRO_TRY(nb.ensure(std::max<uint64_t>(need + (need >> 1), 1ULL << 20)));
     if (ctx->arena_top)
         CORRO_HIP_TRY(hipMemcpyAsync(nb.p, ctx->d_arena.p, ctx->arena_top, hipMemcpyDeviceToDevice, ctx->stream));
     CORRO_HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -579,7 +573,7 @@ int grow_regions(corro_ctx *ctx, uint32_t new_log2S) {
         return fail(CORRO_E_NOMEM, "row store regions would exceed 2^31 entries");
     hipStream_t s = ctx->stream;
     DevBuf nb;
-    TRY(nb.ensure(((size_t)ctx->B << new_log2S) * sizeof(RowEnt)));
+    CORRO_TRY(nb.ensure(((size_t)ctx->B << new_log2S) * sizeof(RowEnt)));
     CORRO_HIP_TRY(hipMemsetAsync(nb.p, 0, ((size_t)ctx->B << new_log2S) * sizeof(RowEnt), s));
     const uint32_t old_log2S = ctx->log2S;
     DevBuf old = ctx->d_ent;
@@ -613,11 +607,11 @@ int grow_heap(corro_ctx *ctx, uint64_t want_records) {
     CORRO_HIP_TRY(hipStreamSynchronize(s));
     top = std::min<unsigned long long>(top, ctx->heap_cap);
     DevBuf nh;
-    TRY(nh.ensure(cap * sizeof(Rec)));
+    CORRO_TRY(nh.ensure(cap * sizeof(Rec)));
     CORRO_HIP_TRY(hipMemcpyAsync(nh.p, ctx->d_heap.p, top * sizeof(Rec), hipMemcpyDeviceToDevice, s));
     DevBuf nts;
     if (ctx->track_ts) {
-        TRY(nts.ensure(cap * 8));
+        CORRO_TRY(nts.ensure(cap * 8));
         CORRO_HIP_TRY(hipMemsetAsync(nts.p, 0, cap * 8, s));
         CORRO_HIP_TRY(hipMemcpyAsync(nts.p, ctx->d_heap_ts.p, top * 8, hipMemcpyDeviceToDevice, s));
     }
@@ -779,12 +773,12 @@ static int upload_site_tables(corro_ctx *ctx) {
         return std::memcmp(ctx->sites[a].data(), ctx->sites[b].data(), 16) < 0;
     });
     for (uint32_t r = 0; r < n; r++) rank[order[r]] = r;
-    TRY(ctx->d_site_rank.ensure(std::max<size_t>(n, 1) * 4));
+    CORRO_TRY(ctx->d_site_rank.ensure(std::max<size_t>(n, 1) * 4));
     CORRO_HIP_TRY(hipMemcpyAsync(ctx->d_site_rank.p, rank.data(), n * 4ULL, hipMemcpyHostToDevice, ctx->stream));
     if (n > ctx->dbv_cap) {
         size_t cap = std::max<size_t>(n, 2 * ctx->dbv_cap);
         DevBuf nb;
-        TRY(nb.ensure(cap * 8));
+        CORRO_TRY(nb.ensure(cap * 8));
         CORRO_HIP_TRY(hipMemsetAsync(nb.p, 0, cap * 8, ctx->stream));
         if (ctx->dbv_cap)
             CORRO_HIP_TRY(hipMemcpyAsync(nb.p, ctx->d_dbv.p, ctx->dbv_cap * 8, hipMemcpyDeviceToDevice, ctx->stream));
@@ -793,7 +787,7 @@ static int upload_site_tables(corro_ctx *ctx) {
         ctx->d_dbv = nb;
         nb.p = nullptr;
         ctx->dbv_cap = cap;
-        TRY(ctx->d_dbv_batch.ensure(cap * 8));
+        CORRO_TRY(ctx->d_dbv_batch.ensure(cap * 8));
     }
     CORRO_HIP_TRY(hipStreamSynchronize(ctx->stream));
     return CORRO_OK;
@@ -849,7 +843,7 @@ static int stage_host_batch(corro_ctx *ctx, const corro_changes *in, BatchDev &b
     size_t total = 0;
     for (auto &x : f)
         if (x.src) total += ((n * x.elem + 255) / 256) * 256;
-    TRY(ctx->d_in.ensure(total));
+    CORRO_TRY(ctx->d_in.ensure(total));
     size_t off = 0;
     for (auto &x : f) {
         if (!x.src) continue;
@@ -902,7 +896,7 @@ static int apply_chunk(corro_ctx *ctx, BatchDev bd, uint8_t *imp_buf) {
     const uint32_t nsites = (uint32_t)ctx->sites.size();
     if (bd.ts && !ctx->track_ts) {
         // timestamps start being tracked: the state so far has zero timestamps
-        TRY(ctx->d_heap_ts.ensure(ctx->heap_cap * 8));
+        CORRO_TRY(ctx->d_heap_ts.ensure(ctx->heap_cap * 8));
         CORRO_HIP_TRY(hipMemsetAsync(ctx->d_heap_ts.p, 0, ctx->heap_cap * 8, s));
         ctx->track_ts = true;
     }
@@ -918,8 +912,8 @@ static int apply_chunk(corro_ctx *ctx, BatchDev bd, uint8_t *imp_buf) {
     tile = (tile + HIST_THREADS - 1) / HIST_THREADS * HIST_THREADS;
     ntiles = (n + tile - 1) / tile;
 
-    TRY(ctx->d_hist.ensure((size_t)ntiles * B * 4));
-    TRY(ctx->d_stage.ensure((size_t)n * sizeof(Rec)));
+    CORRO_TRY(ctx->d_hist.ensure((size_t)ntiles * B * 4));
+    CORRO_TRY(ctx->d_stage.ensure((size_t)n * sizeof(Rec)));
     // (bucket general bits, misc counters, per-site db_version maxima and k_colscan's ticket and status
     // words are zeroed by k_hist)
     const uint32_t scan_wgs = (B + COLSCAN_T - 1) / COLSCAN_T;
@@ -1034,7 +1028,7 @@ static int apply_chunk(corro_ctx *ctx, BatchDev bd, uint8_t *imp_buf) {
         // triage in one pass, queue appends per wave (k_triage); the fast body's workgroups skip it
         static const bool no_triage = std::getenv("CORRO_TRIAGE") && std::atoi(std::getenv("CORRO_TRIAGE")) == 0;
         if (!no_triage) {
-            TRY(ctx->d_fast_of.ensure(B + 256));
+            CORRO_TRY(ctx->d_fast_of.ensure(B + 256));
             a.fast_of = ctx->d_fast_of.as<uint8_t>();
             hipLaunchKernelGGL(k_triage, dim3(std::min<uint32_t>((nblocks + 255) / 256, 1024)), dim3(256), 0, s, a, nblocks,
                                ctx->d_fast_of.as<uint8_t>());
@@ -1086,7 +1080,7 @@ static int apply_chunk(corro_ctx *ctx, BatchDev bd, uint8_t *imp_buf) {
         const uint64_t novf = ctx->h_misc[MISC_OVF];
         if (novf) {
             extra_rounds = true;
-            TRY(run_overflow(ctx, a, novf, n, prof));
+            CORRO_TRY(run_overflow(ctx, a, novf, n, prof));
             ctx->metrics.overflow_rounds++;
             ovf_ms += ctx->last_ms[5];
         }
@@ -1096,11 +1090,11 @@ static int apply_chunk(corro_ctx *ctx, BatchDev bd, uint8_t *imp_buf) {
         // grow what ran out, then merge the deferred buckets again
         const uint64_t why = ctx->h_misc[MISC_DEFER_WHY];
         ctx->metrics.deferred_rounds++;
-        if (why & DEFER_REGION) TRY(grow_regions(ctx, ctx->log2S + 1));
+        if (why & DEFER_REGION) CORRO_TRY(grow_regions(ctx, ctx->log2S + 1));
         if (why & DEFER_HEAP) {
             unsigned long long top = 0;
             CORRO_HIP_TRY(hipMemcpy(&top, ctx->d_heap_top.p, 8, hipMemcpyDeviceToHost));
-            TRY(grow_heap(ctx, std::max<uint64_t>(ctx->heap_cap * 2, top + (top >> 2))));
+            CORRO_TRY(grow_heap(ctx, std::max<uint64_t>(ctx->heap_cap * 2, top + (top >> 2))));
         }
         CORRO_HIP_TRY(hipMemcpyAsync(ctx->d_relist.p, ctx->d_defer.p, ndefer * 4, hipMemcpyDeviceToDevice, s));
         for (int w : {MISC_OVF, MISC_GEN, MISC_WIDEQ, MISC_GEN_SMALL, MISC_GEN_MID, MISC_DEFER, MISC_DEFER_WHY})
@@ -1144,7 +1138,7 @@ static int apply_chunk(corro_ctx *ctx, BatchDev bd, uint8_t *imp_buf) {
     if (ctx->state_rows * 8 > slots * 5) {
         uint32_t lg = ctx->log2S;
         while (((uint64_t)B << lg) / 2 < ctx->state_rows && lg < 26 && ((uint64_t)B << (lg + 1)) <= (1ULL << 31)) lg++;
-        TRY(grow_regions(ctx, lg));
+        CORRO_TRY(grow_regions(ctx, lg));
     }
     return CORRO_OK;
 }
@@ -1164,7 +1158,7 @@ uint64_t corro_detail_chunk_changes(const corro_ctx *ctx) {
 // apply; when it would pass the capacity the exact count is read and the list regrown (contents kept).
 static int touch_reserve(corro_ctx *ctx, uint64_t n) {
     if (!ctx->d_touch_n.p) {
-        TRY(ctx->d_touch_n.ensure(8));
+        CORRO_TRY(ctx->d_touch_n.ensure(8));
         CORRO_HIP_TRY(hipMemsetAsync(ctx->d_touch_n.p, 0, 8, ctx->stream));
     }
     if (ctx->touch_bound + n > ctx->touch_cap) {
@@ -1175,7 +1169,7 @@ static int touch_reserve(corro_ctx *ctx, uint64_t n) {
         if (cur + n > ctx->touch_cap) {
             const uint64_t cap = std::max<uint64_t>(cur + n, std::min<uint64_t>(2 * ctx->touch_cap, cur + 4 * n));
             DevBuf nb;
-            TRY(nb.ensure(cap * 16));
+            CORRO_TRY(nb.ensure(cap * 16));
             if (cur) CORRO_HIP_TRY(hipMemcpyAsync(nb.p, ctx->d_touch.p, cur * 16, hipMemcpyDeviceToDevice, ctx->stream));
             CORRO_HIP_TRY(hipStreamSynchronize(ctx->stream));
             ctx->d_touch.release();
@@ -1239,7 +1233,7 @@ static int apply_batch_impl(corro_ctx *ctx, const corro_changes *in, int mem, co
 
     BatchDev bd{};
     if (mem == CORRO_MEM_HOST) {
-        TRY(stage_host_batch(ctx, in, bd));
+        CORRO_TRY(stage_host_batch(ctx, in, bd));
     } else {
         // k_scatter reads pairs of changes with 16-B (64-bit fields) / 8-B (32-bit fields) loads
         auto misaligned = [](const void *p, uintptr_t a) { return p && ((uintptr_t)p % a) != 0; };
@@ -1288,7 +1282,7 @@ static int apply_batch_impl(corro_ctx *ctx, const corro_changes *in, int mem, co
     if (in->val_off) {
         if (!in->val_size || !in->val_type || !in->val_len || (in->val_data_len && !in->val_data))
             return fail(CORRO_E_INVALID, "long values need val_size, val_type, val_len and val_data");
-        TRY(arena_reserve(ctx, in->val_data_len));
+        CORRO_TRY(arena_reserve(ctx, in->val_data_len));
         if (in->val_data_len)
             CORRO_HIP_TRY(hipMemcpyAsync(ctx->d_arena.as<uint8_t>() + ctx->arena_top, in->val_data, in->val_data_len,
                                          mem == CORRO_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
@@ -1301,10 +1295,10 @@ static int apply_batch_impl(corro_ctx *ctx, const corro_changes *in, int mem, co
     // impact output: a device batch gets its flags written straight into the caller's device
     // buffer; a host batch through a device staging buffer + one copy
     const bool imp_dev = out && out->impact && mem == CORRO_MEM_DEVICE;
-    if (out && out->impact && !imp_dev) TRY(ctx->d_impact.ensure(n));
+    if (out && out->impact && !imp_dev) CORRO_TRY(ctx->d_impact.ensure(n));
     uint8_t *imp_buf = !(out && out->impact) ? nullptr : (imp_dev ? out->impact : ctx->d_impact.as<uint8_t>());
 
-    TRY(affinity_convert(ctx, bd));
+    CORRO_TRY(affinity_convert(ctx, bd));
     // INTEGER-only batch: the scatter stages each change's ts in its record's v1 word (BatchDev::ts_v1;
     // CORRO_TS_V1=0 keeps the per-position ts array, A/B). Otherwise ts must be per position: a
     // position-mode batch that brought its input's per-change ts gets them gathered into that order.
@@ -1316,14 +1310,14 @@ static int apply_batch_impl(corro_ctx *ctx, const corro_changes *in, int mem, co
     if (bd.ts_v1 && !no_ts_pair && ((uintptr_t)bd.ts % 16) == 0) bd.ts_v1 |= 2u;
     if (bd.ap && bd.ts && !bd.ts_pos && !bd.ts_v1) {
         if (!ctx->pm_src) return fail(CORRO_E_INVALID, "internal: position mode without a position -> input map");
-        TRY(ctx->d_pm_ts.ensure(ctx->pm_n * 8 + 8));
+        CORRO_TRY(ctx->d_pm_ts.ensure(ctx->pm_n * 8 + 8));
         hipLaunchKernelGGL(k_ts_by_pos, dim3((uint32_t)std::min<uint64_t>((ctx->pm_n + 255) / 256, 8192)), dim3(256), 0,
                            ctx->stream, bd.ts, ctx->pm_src, ctx->pm_n, ctx->d_pm_ts.as<uint64_t>());
         CORRO_HIP_TRY(hipGetLastError());
         bd.ts = ctx->d_pm_ts.as<uint64_t>();
         bd.ts_pos = 1;
     }
-    if (ctx->track_touched) TRY(touch_reserve(ctx, n));
+    if (ctx->track_touched) CORRO_TRY(touch_reserve(ctx, n));
     // (a slot layout carries its padding: up to a quarter more slots than applied records, one chunk still)
     const uint64_t chunk = ctx->pm_ap ? std::max<uint64_t>(n, 1) : ctx->slot_rec ? chunk_cap : corro_detail_chunk_changes(ctx);
     // (slot mode: corro_partition_slots validated the records it packed and marks a failed batch's
@@ -1350,7 +1344,7 @@ static int apply_batch_impl(corro_ctx *ctx, const corro_changes *in, int mem, co
         adv(c.conv), adv(c.cv0), adv(c.cv1), adv(c.cmeta), adv(c.slot_rec);
         c.slot_base = (uint32_t)off;
         c.n = m;
-        TRY(apply_chunk(ctx, c, imp_buf ? imp_buf + off : nullptr));
+        CORRO_TRY(apply_chunk(ctx, c, imp_buf ? imp_buf + off : nullptr));
         for (int k = 0; k < 6; k++) ms[k] += ctx->last_ms[k];
     }
     for (int k = 0; k < 6; k++) ctx->last_ms[k] = ms[k];
@@ -1414,9 +1408,9 @@ int state_dense_view(corro_ctx *ctx, DenseView &v) {
     const uint32_t nb = (uint32_t)std::max<uint64_t>(1, (m + chunk - 1) / chunk);
     hipStream_t s = ctx->stream;
     if (ctx->dense_epoch != ctx->state_epoch) {
-        TRY(ctx->d_dense.ensure(std::max<uint64_t>(m, 1) * sizeof(Rec)));
-        if (ctx->track_ts) TRY(ctx->d_dense_ts.ensure(std::max<uint64_t>(m, 1) * 8));
-        TRY(ctx->d_dense_view.ensure(nb * 12ULL + 256));
+        CORRO_TRY(ctx->d_dense.ensure(std::max<uint64_t>(m, 1) * sizeof(Rec)));
+        if (ctx->track_ts) CORRO_TRY(ctx->d_dense_ts.ensure(std::max<uint64_t>(m, 1) * 8));
+        CORRO_TRY(ctx->d_dense_view.ensure(nb * 12ULL + 256));
         std::vector<uint64_t> off(nb);
         std::vector<uint32_t> cnt(nb);
         for (uint32_t b = 0; b < nb; b++) {
@@ -1466,7 +1460,7 @@ int set_db_versions(corro_ctx *ctx, const std::vector<std::pair<uint32_t, uint64
         if (best[t]) flat.insert(flat.end(), {(uint64_t)t, best[t]});
     const uint32_t n = (uint32_t)(flat.size() / 2);
     CORRO_HIP_TRY(hipSetDevice(ctx->device));
-    TRY(ctx->d_setdbv.ensure(flat.size() * 8 + 256));
+    CORRO_TRY(ctx->d_setdbv.ensure(flat.size() * 8 + 256));
     hipStream_t s = ctx->stream;
     CORRO_HIP_TRY(hipMemcpyAsync(ctx->d_setdbv.p, flat.data(), flat.size() * 8, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_set_dbv, dim3((n + 255) / 256), dim3(256), 0, s, ctx->d_setdbv.as<uint64_t>(), n,
@@ -1567,7 +1561,7 @@ int corro_state_export(corro_ctx *ctx, corro_rows *o, uint64_t cap, uint64_t *wr
     hipStream_t s = ctx->stream;
     // device SoA: 8*7 + 4*3 + 1*2 bytes per row
     const size_t per = 8 * 7 + 4 * 3 + 2;
-    TRY(ctx->d_export.ensure(m * per + 13 * 256 + 256));
+    CORRO_TRY(ctx->d_export.ensure(m * per + 13 * 256 + 256));
     uint8_t *p = ctx->d_export.as<uint8_t>();
     corro_rows d{};
     auto carve = [&](size_t elem) {
@@ -1637,7 +1631,7 @@ int corro_value_bytes(corro_ctx *ctx, const uint64_t *handles, uint64_t n, uint8
     CORRO_HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     DevBuf &tmp = ctx->d_export;  // (scratch shared with corro_state_export)
-    TRY(tmp.ensure(16 * n + total + 256));
+    CORRO_TRY(tmp.ensure(16 * n + total + 256));
     uint64_t *dh = tmp.as<uint64_t>(), *doff = dh + n;
     uint8_t *dout = reinterpret_cast<uint8_t *>(doff + n);
     CORRO_HIP_TRY(hipMemcpyAsync(dh, handles, 8 * n, hipMemcpyHostToDevice, s));
@@ -1654,7 +1648,7 @@ int corro_ctx_track_touched(corro_ctx *ctx, int on) {
     if (!ctx) return fail(CORRO_E_INVALID, "NULL argument");
     CORRO_HIP_TRY(hipSetDevice(ctx->device));
     ctx->track_touched = on != 0;
-    TRY(ctx->d_touch_n.ensure(8));
+    CORRO_TRY(ctx->d_touch_n.ensure(8));
     CORRO_HIP_TRY(hipMemsetAsync(ctx->d_touch_n.p, 0, 8, ctx->stream));
     CORRO_HIP_TRY(hipStreamSynchronize(ctx->stream));
     ctx->touch_bound = 0;
@@ -1683,15 +1677,15 @@ int corro_state_export_touched(corro_ctx *ctx, corro_rows *o, uint64_t cap, uint
     // dedup stamps per region entry: reallocated (zeroed) when the regions changed size
     const uint64_t nent = (uint64_t)ctx->B << ctx->log2S;
     if (ctx->touch_stamp_n != nent || ++ctx->touch_epoch == 0) {
-        TRY(ctx->d_touch_stamp.ensure(nent * 4));
+        CORRO_TRY(ctx->d_touch_stamp.ensure(nent * 4));
         CORRO_HIP_TRY(hipMemsetAsync(ctx->d_touch_stamp.p, 0, nent * 4, s));
         ctx->touch_stamp_n = nent;
         ctx->touch_epoch = 1;
     }
     size_t temp = 0;
-    TRY(prim_inclusive_scan_u32(nullptr, &temp, nullptr, nullptr, (uint32_t)m, s));
+    CORRO_TRY(prim_inclusive_scan_u32(nullptr, &temp, nullptr, nullptr, (uint32_t)m, s));
     const size_t col = ((m * 4 + 255) / 256) * 256;
-    TRY(ctx->d_touch_tmp.ensure(3 * col + temp + 256));
+    CORRO_TRY(ctx->d_touch_tmp.ensure(3 * col + temp + 256));
     uint32_t *ent = ctx->d_touch_tmp.as<uint32_t>();
     uint32_t *cnt = (uint32_t *)((uint8_t *)ent + col), *incl = (uint32_t *)((uint8_t *)ent + 2 * col);
     void *tmp = (uint8_t *)ent + 3 * col;
@@ -1699,7 +1693,7 @@ int corro_state_export_touched(corro_ctx *ctx, corro_rows *o, uint64_t cap, uint
     hipLaunchKernelGGL(k_touch_count, grid, dim3(256), 0, s, row_store(ctx), ctx->log2B, ctx->d_touch.as<uint4>(), m,
                        ctx->d_touch_stamp.as<uint32_t>(), ctx->touch_epoch, ent, cnt);
     CORRO_HIP_TRY(hipGetLastError());
-    TRY(prim_inclusive_scan_u32(tmp, &temp, cnt, incl, (uint32_t)m, s));
+    CORRO_TRY(prim_inclusive_scan_u32(tmp, &temp, cnt, incl, (uint32_t)m, s));
     uint32_t total = 0;
     CORRO_HIP_TRY(hipMemcpyAsync(&total, incl + (m - 1), 4, hipMemcpyDeviceToHost, s));
     CORRO_HIP_TRY(hipStreamSynchronize(s));
@@ -1708,7 +1702,7 @@ int corro_state_export_touched(corro_ctx *ctx, corro_rows *o, uint64_t cap, uint
         return fail(CORRO_E_RANGE, "touched rows exceed cap (*written = the row count)");
     }
     const size_t per = 8 * 7 + 4 * 3 + 2;
-    TRY(ctx->d_export.ensure((uint64_t)total * per + 13 * 256 + 256));
+    CORRO_TRY(ctx->d_export.ensure((uint64_t)total * per + 13 * 256 + 256));
     uint8_t *p = ctx->d_export.as<uint8_t>();
     corro_rows d{};
     auto carve = [&](size_t elem) {

@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "internal.h"
+#include "scratch_core.h"
 
 namespace corro {
 
@@ -330,7 +331,6 @@ uint32_t bits_for(uint64_t v) {
     return b;
 }
 
-size_t al(size_t bytes) { return ((bytes + 255) / 256) * 256; }
 
 // Build (or reuse) the (site, db_version, seq) index of the current state.
 int ensure_index(corro_ctx *ctx, XIndex &x, XParams &p) {
@@ -353,14 +353,14 @@ int ensure_index(corro_ctx *ctx, XIndex &x, XParams &p) {
                 return rc;
             if (int rc = prim_inclusive_scan_u32(nullptr, &scan_tmp, nullptr, nullptr, (uint32_t)m, s)) return rc;
         }
-        const size_t idx_bytes = al(m * 8) + 5 * al(m * 4 + 4) + al(m * 8 + 8) + al(m * 64) + al(m * 8);
-        const size_t scr_bytes = 2 * al(m * 8) + al(m * 4) + al(B * 8ULL) + al(B * 16ULL) + 256 +
-                                 al(std::max(sort_tmp, scan_tmp) + 256);
+        const size_t idx_bytes = al256(m * 8) + 5 * al256(m * 4 + 4) + al256(m * 8 + 8) + al256(m * 64) + al256(m * 8);
+        const size_t scr_bytes = 2 * al256(m * 8) + al256(m * 4) + al256(B * 8ULL) + al256(B * 16ULL) + 256 +
+                                 al256(std::max(sort_tmp, scan_tmp) + 256);
         if (int rc = ctx->d_xidx.ensure(idx_bytes + scr_bytes)) return rc;
         uint8_t *q = ctx->d_xidx.as<uint8_t>();
         auto carve = [&](size_t bytes) {
             uint8_t *r = q;
-            q += al(bytes);
+            q += al256(bytes);
             return r;
         };
         ctx->x.hkey = (uint64_t *)carve(m * 8);
@@ -476,16 +476,16 @@ extern "C" int corro_extract_changes(corro_ctx *ctx, const corro_extract_in *in,
     }
     // device scratch: staged needs (host mode), outputs (host mode), out_src
     const bool has_seq = in->seq_start != nullptr;
-    size_t need_bytes = mem == CORRO_MEM_HOST ? al(n * 4) + 2 * al(n * 8) + (has_seq ? 2 * al(n * 4) : 0) : 0;
+    size_t need_bytes = mem == CORRO_MEM_HOST ? al256(n * 4) + 2 * al256(n * 8) + (has_seq ? 2 * al256(n * 4) : 0) : 0;
     size_t out_bytes = 0;
     if (mem == CORRO_MEM_HOST)
-        out_bytes = pass == 0 ? 2 * al(n * 8) : 2 * al((n + 1) * 8) + 5 * al(G * 8) + al(R * 8) * 7 + al(R * 4) * 3 + al(R) * 2;
-    const size_t src_bytes = pass == 1 ? al(R * 4 + 4) : 0;
+        out_bytes = pass == 0 ? 2 * al256(n * 8) : 2 * al256((n + 1) * 8) + 5 * al256(G * 8) + al256(R * 8) * 7 + al256(R * 4) * 3 + al256(R) * 2;
+    const size_t src_bytes = pass == 1 ? al256(R * 4 + 4) : 0;
     if (int rc = ctx->d_xout.ensure(need_bytes + out_bytes + src_bytes + 1024)) return rc;
     uint8_t *q = ctx->d_xout.as<uint8_t>();
     auto carve = [&](size_t bytes) {
         uint8_t *r = q;
-        q += al(bytes);
+        q += al256(bytes);
         return r;
     };
     if (mem == CORRO_MEM_HOST) {

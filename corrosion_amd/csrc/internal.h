@@ -33,6 +33,12 @@ int fail(int code, const std::string &msg);
         if (e_ != hipSuccess)                                                            \
             return ::corro::fail(CORRO_E_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
     } while (0)
+// a failed call of the library's own (its error is already set) ends the caller with the same code
+#define CORRO_TRY(...)                   \
+    do {                                 \
+        int rc_ = (__VA_ARGS__);         \
+        if (rc_ != CORRO_OK) return rc_; \
+    } while (0)
 
 // One staged / state record: a column change or a clock row (64 B, 16-B aligned so a lane moves
 // it with four dwordx4 accesses). `pos` orders records of one row: prior-state rows use their

@@ -22,16 +22,15 @@
 //   k_tl_frames  flat over the output bytes: one lane per aligned 16-byte piece of the buffer (a frame
 //                is 49 or 55 bytes, so a piece holds bytes of at most two), one 16-byte store where
 //                the piece lies inside the buffer and byte stores at its two ends; and frame_off
-//   k_tl_fold    the error flags: every workgroup of the check and of the count stores one partial
+//   k_flag_fold  (scratch.h) the error flags: every workgroup of the check and of the count stores one partial
 //                word, one workgroup folds them (no same-address atomic per wave, DESIGN section 5
 //                round 4), and the total next to them: one read-back
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstring>
-#include <vector>
 
 #include "internal.h"
+#include "scratch.h"
 
 namespace corro {
 int prim_inclusive_sum_u64(void *temp, size_t *temp_bytes, const uint64_t *in, uint64_t *out, uint64_t n, hipStream_t s);
@@ -82,11 +81,6 @@ __device__ inline bool same_site(const uint64_t *off, uint32_t nsites, uint64_t 
     return u <= nsites && off[u] != i + 1;
 }
 
-__device__ inline void wg_flag(uint32_t *part, bool bad) {
-    const int any = __syncthreads_or(bad ? 1 : 0);
-    if (threadIdx.x == 0) part[blockIdx.x] = any ? 1u : 0u;
-}
-
 __global__ void k_tl_check(TlDev d) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const corro_tails_in &in = d.in;
@@ -111,17 +105,6 @@ __global__ void k_tl_check(TlDev d) {
         if (i + 1 < in.book_nbuf && same_site(in.buf_off, S, i)) bad |= in.buf_version[i] >= in.buf_version[i + 1];
     }
     wg_flag(d.part_check, bad);
-}
-
-// One workgroup: misc[0] |= any partial; misc[1] = *total (when given).
-__global__ void k_tl_fold(const uint32_t *part, uint64_t n, unsigned long long *misc, const uint64_t *total) {
-    bool bad = false;
-    for (uint64_t i = threadIdx.x; i < n; i += blockDim.x) bad |= part[i] != 0;
-    const int any = __syncthreads_or(bad ? 1 : 0);
-    if (threadIdx.x == 0) {
-        if (any) misc[0] = 1;
-        if (total) misc[1] = *total;
-    }
 }
 
 // One need. FILL = false: the group check (bad), need_host and the count; FILL = true: the ranges, at
@@ -273,34 +256,10 @@ __global__ void k_tl_frames(TlDev d, uint64_t nranges, uint64_t nbytes, uint32_t
     }
 }
 
-size_t al(size_t b) { return ((b + 255) / 256) * 256; }
-
-struct Carver {
-    uint8_t *q = nullptr;
-    template <class T> T *take(size_t count) {
-        uint8_t *r = q;
-        q += al(count * sizeof(T));
-        return reinterpret_cast<T *>(r);
-    }
-};
-
-dim3 grid_for(uint64_t n) { return dim3((uint32_t)((n + 255) / 256)); }
-
 }  // namespace
 }  // namespace corro
 
 using namespace corro;
-
-#define TL_LAUNCH(kernel, count, ...)                                                      \
-    do {                                                                                   \
-        hipLaunchKernelGGL(kernel, grid_for(std::max<uint64_t>(count, 1)), dim3(256), 0, s, __VA_ARGS__); \
-        CORRO_HIP_TRY(hipGetLastError());                                                  \
-    } while (0)
-#define TL_TRY(x)                        \
-    do {                                 \
-        int rc_ = (x);                   \
-        if (rc_ != CORRO_OK) return rc_; \
-    } while (0)
 
 extern "C" int corro_need_tails(corro_ctx *ctx, const corro_tails_in *in, int mem, corro_tails_out *out, int pass) {
     if (!ctx || !in || !out) return fail(CORRO_E_INVALID, "NULL argument");
@@ -345,67 +304,49 @@ extern "C" int corro_need_tails(corro_ctx *ctx, const corro_tails_in *in, int me
     const uint64_t ncheck = std::max({T, E, (uint64_t)S, NG, NB}) + 1;
     const uint64_t wg_check = (ncheck + 255) / 256, wg_count = (std::max<uint64_t>(T, 1) + 255) / 256;
     size_t temp = 0;
-    TL_TRY(prim_inclusive_sum_u64(nullptr, &temp, nullptr, nullptr, std::max<uint64_t>(T, 1), s));
+    CORRO_TRY(prim_inclusive_sum_u64(nullptr, &temp, nullptr, nullptr, std::max<uint64_t>(T, 1), s));
     temp += 256;
-    const size_t stage = host ? 3 * al(T + 1) + al(T * 4 + 4) + 3 * al((T + 1) * 8) + al((E + 1) * 8) + al(G * 8 + 8) +
-                                    2 * al((S + 1) * 8ull) + 2 * al(NG * 8 + 8) + al(NB * 8 + 8)
-                              : 0;
-    TL_TRY(ctx->d_reqdec[0].ensure(256 + al(wg_check * 4) + al(wg_count * 4) + 2 * al((T + 1) * 8) + al(T + 1) + al(temp) +
-                                   al(nsites * 16 + 16) + stage));
-    Carver c0{ctx->d_reqdec[0].as<uint8_t>()};
-    d.misc = c0.take<unsigned long long>(32);
-    d.part_check = c0.take<uint32_t>(wg_check);
-    d.part_count = c0.take<uint32_t>(wg_count);
-    d.cnt = c0.take<uint64_t>(T + 1);
-    d.off = c0.take<uint64_t>(T + 1);
-    d.host = c0.take<uint8_t>(T + 1);
-    void *tmp = c0.take<uint8_t>(temp);
-    {
-        uint8_t *ds = c0.take<uint8_t>(nsites * 16 + 16);
-        std::vector<uint8_t> hs(nsites * 16 + 16, 0);
-        for (size_t i = 0; i < nsites; i++) std::memcpy(hs.data() + 16 * i, ctx->sites[i].data(), 16);
-        CORRO_HIP_TRY(hipMemcpy(ds, hs.data(), nsites * 16 + 16, hipMemcpyHostToDevice));
-        d.sites = ds;
-    }
-    if (host) {
-        bool ok = true;
-        auto up = [&](const void *src, size_t b, size_t room) -> const void * {
-            uint8_t *dst = c0.take<uint8_t>(room);
-            if (b && hipMemcpyAsync(dst, src, b, hipMemcpyHostToDevice, s) != hipSuccess) ok = false;
-            return dst;
-        };
-        d.in.kind = (const uint8_t *)up(in->kind, T, T + 1);
-        d.in.need_keep = (const uint8_t *)up(in->need_keep, T, T + 1);
-        d.in.in_state = (const uint8_t *)up(in->in_state, T, T + 1);
-        d.in.need_site = (const uint32_t *)up(in->need_site, T * 4, T * 4 + 4);
-        d.in.start = (const uint64_t *)up(in->start, T * 8, (T + 1) * 8);
-        d.in.end = (const uint64_t *)up(in->end, T * 8, (T + 1) * 8);
-        d.in.need_ent_off = (const uint64_t *)up(in->need_ent_off, (T + 1) * 8, (T + 1) * 8);
-        d.in.grp_off = (const uint64_t *)up(in->grp_off, (E + 1) * 8, (E + 1) * 8);
-        d.in.version = (const int64_t *)up(in->version, G * 8, G * 8 + 8);
+    Stager st{s, host};
+    void *tmp = nullptr;
+    uint8_t *dsites = nullptr;
+    CORRO_TRY(carve(ctx->d_reqdec[0], [&](Carver &c) {
+        d.misc = c.take<unsigned long long>(32);
+        d.part_check = c.take<uint32_t>(wg_check);
+        d.part_count = c.take<uint32_t>(wg_count);
+        d.cnt = c.take<uint64_t>(T + 1);
+        d.off = c.take<uint64_t>(T + 1);
+        d.host = c.take<uint8_t>(T + 1);
+        tmp = c.take<uint8_t>(temp);
+        d.sites = dsites = c.take<uint8_t>(nsites * 16 + 16);
+        d.in.kind = c.up(in->kind, T, T + 1);
+        d.in.need_keep = c.up(in->need_keep, T, T + 1);
+        d.in.in_state = c.up(in->in_state, T, T + 1);
+        d.in.need_site = c.up(in->need_site, T * 4, T * 4 + 4);
+        d.in.start = c.up(in->start, T * 8, (T + 1) * 8);
+        d.in.end = c.up(in->end, T * 8, (T + 1) * 8);
+        d.in.need_ent_off = c.up(in->need_ent_off, (T + 1) * 8, (T + 1) * 8);
+        d.in.grp_off = c.up(in->grp_off, (E + 1) * 8, (E + 1) * 8);
+        d.in.version = c.up(in->version, G * 8, G * 8 + 8);
         if (any_book) {
-            d.in.gap_off = (const uint64_t *)up(in->gap_off, (S + 1) * 8ull, (S + 1) * 8ull);
-            d.in.buf_off = (const uint64_t *)up(in->buf_off, (S + 1) * 8ull, (S + 1) * 8ull);
-            d.in.gap_start = (const uint64_t *)up(in->gap_start, NG * 8, NG * 8 + 8);
-            d.in.gap_end = (const uint64_t *)up(in->gap_end, NG * 8, NG * 8 + 8);
-            d.in.buf_version = (const uint64_t *)up(in->buf_version, NB * 8, NB * 8 + 8);
+            d.in.gap_off = c.up(in->gap_off, (S + 1) * 8ull, (S + 1) * 8ull);
+            d.in.buf_off = c.up(in->buf_off, (S + 1) * 8ull, (S + 1) * 8ull);
+            d.in.gap_start = c.up(in->gap_start, NG * 8, NG * 8 + 8);
+            d.in.gap_end = c.up(in->gap_end, NG * 8, NG * 8 + 8);
+            d.in.buf_version = c.up(in->buf_version, NB * 8, NB * 8 + 8);
         }
-        if (!ok) return fail(CORRO_E_DEVICE, "upload of the needs failed");
-    }
+    }, &st));
+    if (!st.ok) return fail(CORRO_E_DEVICE, "upload of the needs failed");
+    CORRO_TRY(upload_site_table(ctx, dsites, s));
     CORRO_HIP_TRY(hipMemsetAsync(d.misc, 0, 256, s));
     CORRO_HIP_TRY(hipMemsetAsync(d.off, 0, 8, s));
-    TL_LAUNCH(k_tl_check, ncheck, d);
-    hipLaunchKernelGGL(k_tl_fold, dim3(1), dim3(256), 0, s, (const uint32_t *)d.part_check, wg_check, d.misc,
-                       (const uint64_t *)nullptr);
-    CORRO_HIP_TRY(hipGetLastError());
-    TL_LAUNCH(k_tl_count, T, d);
+    CORRO_LAUNCH(k_tl_check, grid_for(ncheck), d);
+    CORRO_LAUNCH(k_flag_fold, dim3(1), d.part_check, wg_check, d.misc, fold_totals(0, {}));
+    CORRO_LAUNCH(k_tl_count, grid_for(std::max<uint64_t>(T, 1)), d);
     if (T) {
         size_t t = temp;
-        TL_TRY(prim_inclusive_sum_u64(tmp, &t, d.cnt, d.off + 1, T, s));
+        CORRO_TRY(prim_inclusive_sum_u64(tmp, &t, d.cnt, d.off + 1, T, s));
     }
-    hipLaunchKernelGGL(k_tl_fold, dim3(1), dim3(256), 0, s, (const uint32_t *)d.part_count, wg_count, d.misc,
-                       (const uint64_t *)(d.off + T));
-    CORRO_HIP_TRY(hipGetLastError());
+    CORRO_LAUNCH(k_flag_fold, dim3(1), d.part_count, wg_count, d.misc, fold_totals(1, {d.off + T}));
     unsigned long long misc[2] = {0, 0};
     CORRO_HIP_TRY(hipMemcpyAsync(misc, d.misc, sizeof(misc), hipMemcpyDeviceToHost, s));
     CORRO_HIP_TRY(hipStreamSynchronize(s));
@@ -435,31 +376,25 @@ extern "C" int corro_need_tails(corro_ctx *ctx, const corro_tails_in *in, int me
         return CORRO_OK;
     }
     corro_tails_out o = *out;
-    TL_TRY(ctx->d_reqdec[1].ensure(al(N * 4) + (host ? 2 * al(N * 8) + al(NBY + 16) + al((N + 1) * 8) : 0)));
-    Carver c1{ctx->d_reqdec[1].as<uint8_t>()};
-    d.range_site = c1.take<uint32_t>(N);
-    if (host) {
-        o.range_start = c1.take<uint64_t>(N);
-        o.range_end = c1.take<uint64_t>(N);
-        o.buf = c1.take<uint8_t>(NBY + 16);
-        o.frame_off = c1.take<uint64_t>(N + 1);
-    }
+    CORRO_TRY(carve(ctx->d_reqdec[1], [&](Carver &c) {
+        d.range_site = c.take<uint32_t>(N);
+        if (host) {
+            o.range_start = c.take<uint64_t>(N);
+            o.range_end = c.take<uint64_t>(N);
+            o.buf = c.take<uint8_t>(NBY + 16);
+            o.frame_off = c.take<uint64_t>(N + 1);
+        }
+    }));
     d.out = o;
-    TL_LAUNCH(k_tl_fill, T, d);
+    CORRO_LAUNCH(k_tl_fill, grid_for(std::max<uint64_t>(T, 1)), d);
     const uint32_t lead = (uint32_t)(reinterpret_cast<uintptr_t>(o.buf) & 15);
     const uint64_t npieces = (lead + NBY + 15) / 16;
-    TL_LAUNCH(k_tl_frames, std::max(npieces, N + 1), d, N, NBY, lead, npieces);
-    if (host) {
-        bool ok = true;
-        auto down = [&](void *dst, const void *src, size_t b) {
-            if (hipMemcpyAsync(dst, src, b, hipMemcpyDeviceToHost, s) != hipSuccess) ok = false;
-        };
-        down(out->range_start, o.range_start, N * 8);
-        down(out->range_end, o.range_end, N * 8);
-        down(out->buf, o.buf, NBY);
-        down(out->frame_off, o.frame_off, (N + 1) * 8);
-        if (!ok) return fail(CORRO_E_DEVICE, "download of the tails failed");
-    }
+    CORRO_LAUNCH(k_tl_frames, grid_for(std::max(npieces, N + 1)), d, N, NBY, lead, npieces);
+    st.down(out->range_start, o.range_start, N * 8);
+    st.down(out->range_end, o.range_end, N * 8);
+    st.down(out->buf, o.buf, NBY);
+    st.down(out->frame_off, o.frame_off, (N + 1) * 8);
+    if (!st.ok) return fail(CORRO_E_DEVICE, "download of the tails failed");
     CORRO_HIP_TRY(hipStreamSynchronize(s));
     return CORRO_OK;
 }

@@ -15,12 +15,6 @@
 #include "internal.h"
 #include "rowhash.h"
 
-#define TRY_PART(x)                      \
-    do {                                 \
-        int rc_ = (x);                   \
-        if (rc_ != CORRO_OK) return rc_; \
-    } while (0)
-
 namespace corro {
 int prim_inclusive_scan_u32(void *temp, size_t *temp_bytes, const uint32_t *in, uint32_t *out, uint32_t n,
                             hipStream_t s);
@@ -682,7 +676,7 @@ extern "C" int corro_partition_var(corro_ctx *ctx, const corro_changes *in, uint
     if (n == 0) return CORRO_OK;
     CORRO_HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    TRY_PART(pk_mirror_sync(ctx));
+    CORRO_TRY(pk_mirror_sync(ctx));
     uint64_t max_pk = 0;
     for (const PkTable &t : ctx->pk) max_pk = std::max<uint64_t>(max_pk, t.interned ? t.max_len : 0);
     if (in->val_data_len + (uint64_t)n * max_pk >= (1ULL << 32))
@@ -702,7 +696,7 @@ extern "C" int corro_partition_var(corro_ctx *ctx, const corro_changes *in, uint
     hipLaunchKernelGGL(k_part_scan, dim3(1), dim3(64), 0, s, d_counts, ntiles, nranks, d_tot);
     // scratch: perm (caller's or ours), vlen, vincl, rocPRIM temp, segment / record bases
     size_t temp = 0;
-    TRY_PART(prim_inclusive_scan_u32(nullptr, &temp, nullptr, nullptr, n, s));
+    CORRO_TRY(prim_inclusive_scan_u32(nullptr, &temp, nullptr, nullptr, n, s));
     const size_t col = ((size_t)n * 4 + 255) & ~(size_t)255;
     if (int rc = ctx->d_part_var.ensure(3 * col + temp + 2 * 64 * 8 + 256)) return rc;
     uint8_t *sp = ctx->d_part_var.as<uint8_t>();
@@ -714,7 +708,7 @@ extern "C" int corro_partition_var(corro_ctx *ctx, const corro_changes *in, uint
     hipLaunchKernelGGL(k_partv_pack, dim3(ntiles), dim3(PART_THREADS), 0, s, bd, dir, ntables, tile, nranks, d_counts,
                        static_cast<PackedRec80 *>(out), d_perm, vlen);
     CORRO_HIP_TRY(hipGetLastError());
-    TRY_PART(prim_inclusive_scan_u32(tmp, &temp, vlen, vincl, n, s));
+    CORRO_TRY(prim_inclusive_scan_u32(tmp, &temp, vlen, vincl, n, s));
     CORRO_HIP_TRY(hipMemcpyAsync(counts, d_tot, nranks * 8ULL, hipMemcpyDeviceToHost, s));
     CORRO_HIP_TRY(hipStreamSynchronize(s));
     // per-rank record and byte bases: B(x) = bytes of records [0, x) = vincl[x - 1]

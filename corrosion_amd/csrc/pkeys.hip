@@ -37,12 +37,7 @@
 #include <vector>
 
 #include "internal.h"
-
-#define TRY_PK(x)                        \
-    do {                                 \
-        int rc_ = (x);                   \
-        if (rc_ != CORRO_OK) return rc_; \
-    } while (0)
+#include "scratch_core.h"
 
 namespace corro {
 
@@ -926,10 +921,9 @@ int pk_place_ordered(corro_ctx *ctx, const PkTable &t, PkSlot *slots, uint64_t n
     if (int rc = ovf_sort_pairs(nullptr, &temp, nullptr, nullptr, nullptr, nullptr, (uint32_t)n, bits, s)) return rc;
     if (int rc = prim_inclusive_max_u64(nullptr, &t1, nullptr, nullptr, n, s)) return rc;
     temp = std::max(temp, t1);
-    auto al = [](uint64_t x) { return (x + 255) & ~255ULL; };
-    const uint64_t c8 = al(n * 8), c4 = al(n * 4);
+    const uint64_t c8 = al256(n * 8), c4 = al256(n * 4);
     DevBuf sc;
-    if (sc.ensure(2 * c8 + 2 * c4 + 256 + al(temp)) != CORRO_OK) return CORRO_OK;  // (no room: rebuild by claims)
+    if (sc.ensure(2 * c8 + 2 * c4 + 256 + al256(temp)) != CORRO_OK) return CORRO_OK;  // (no room: rebuild by claims)
     uint8_t *b = sc.as<uint8_t>();
     uint64_t *ki = reinterpret_cast<uint64_t *>(b), *ko = reinterpret_cast<uint64_t *>(b + c8);
     uint32_t *vi = reinterpret_cast<uint32_t *>(b + 2 * c8), *vo = reinterpret_cast<uint32_t *>(b + 2 * c8 + c4);
@@ -1009,13 +1003,12 @@ int pk_keys_device(corro_ctx *ctx, uint32_t table, const PkRefs &r, uint64_t n, 
     hipStream_t s = ctx->stream;
     CORRO_HIP_TRY(hipSetDevice(ctx->device));
     // per-change columns (al256 each) + counters + rocPRIM temp
-    auto al = [](uint64_t x) { return (x + 255) & ~255ULL; };
     size_t temp = 0, t1 = 0;
     if (int rc = prim_inclusive_scan_u32(nullptr, &temp, nullptr, nullptr, (uint32_t)n, s)) return rc;
     if (int rc = prim_inclusive_scan_u32_u64(nullptr, &t1, nullptr, nullptr, n, s)) return rc;
     temp = std::max(temp, t1);
-    const uint64_t c4 = al(n * 4), c8 = al(n * 8);
-    const uint64_t need = 8 * c4 + 3 * c8 + 256 + al(temp);
+    const uint64_t c4 = al256(n * 4), c8 = al256(n * 8);
+    const uint64_t need = 8 * c4 + 3 * c8 + 256 + al256(temp);
     if (int rc = ctx->d_pk_scratch.ensure(need)) return rc;
     uint8_t *base = ctx->d_pk_scratch.as<uint8_t>();
     PkArgs a{};
@@ -1043,7 +1036,7 @@ int pk_keys_device(corro_ctx *ctx, uint32_t table, const PkRefs &r, uint64_t n, 
     a.h = (uint64_t *)take(c8);
     a.noff = (uint64_t *)take(c8);
     a.ctl = (unsigned long long *)take(256);
-    void *d_temp = take(al(temp));
+    void *d_temp = take(al256(temp));
     if (t.interned) {
         if (t.n + n > ((uint64_t)PK_NEW - 1)) return fail(CORRO_E_RANGE, "interned pk table past 2^31 keys");
         // slots for the held keys and a share of the call's at load <= 3/4; a call that brings more new
@@ -1053,7 +1046,7 @@ int pk_keys_device(corro_ctx *ctx, uint32_t table, const PkRefs &r, uint64_t n, 
         // sixty-fourth into one that holds keys.)
         const uint64_t est_new = std::max<uint64_t>(t.n ? n / 64 : n / 16, 1ULL << 16);
         const uint64_t want = t.n + est_new;
-        if (t.nslots < pk_slots_for(want, 3, 4)) TRY_PK(pk_slots_resize(ctx, t, want));
+        if (t.nslots < pk_slots_for(want, 3, 4)) CORRO_TRY(pk_slots_resize(ctx, t, want));
         a.koff = t.d_off.as<uint64_t>();
         a.kbytes = t.d_bytes.as<uint8_t>();
         a.khash = t.d_hash.as<uint64_t>();
@@ -1148,7 +1141,7 @@ int pk_keys_device(corro_ctx *ctx, uint32_t table, const PkRefs &r, uint64_t n, 
 #undef HIP_PKC
     // the next call starts at load <= 0.6; a call that placed a quarter of the keys by claims leaves
     // them rebuilt in home order (sized the same way: the next call's own pre-sizing would rebuild again)
-    if (4 * t.n > 3 * t.nslots || (nnew >= 65536 && 4ULL * nnew >= t.n)) TRY_PK(pk_slots_resize(ctx, t, t.n + t.n / 4));
+    if (4 * t.n > 3 * t.nslots || (nnew >= 65536 && 4ULL * nnew >= t.n)) CORRO_TRY(pk_slots_resize(ctx, t, t.n + t.n / 4));
     return CORRO_OK;
 }
 

@@ -28,6 +28,7 @@
 #include <algorithm>
 
 #include "internal.h"
+#include "scratch.h"
 
 namespace corro {
 int prim_inclusive_sum_u64(void *temp, size_t *temp_bytes, const uint64_t *in, uint64_t *out, uint64_t n, hipStream_t s);
@@ -364,34 +365,10 @@ __global__ void k_sp_fill(SpDev d, uint64_t nspans) {
     d.out.row_count[i] = rn;
 }
 
-size_t al(size_t b) { return ((b + 255) / 256) * 256; }
-
-struct Carver {
-    uint8_t *q = nullptr;
-    template <class T> T *take(size_t count) {
-        uint8_t *r = q;
-        q += al(count * sizeof(T));
-        return reinterpret_cast<T *>(r);
-    }
-};
-
-dim3 grid_for(uint64_t n) { return dim3((uint32_t)((n + 255) / 256)); }
-
 }  // namespace
 }  // namespace corro
 
 using namespace corro;
-
-#define RD_LAUNCH(kernel, count, ...)                                                      \
-    do {                                                                                   \
-        hipLaunchKernelGGL(kernel, grid_for(std::max<uint64_t>(count, 1)), dim3(256), 0, s, __VA_ARGS__); \
-        CORRO_HIP_TRY(hipGetLastError());                                                  \
-    } while (0)
-#define RD_TRY(x)                        \
-    do {                                 \
-        int rc_ = (x);                   \
-        if (rc_ != CORRO_OK) return rc_; \
-    } while (0)
 
 extern "C" int corro_decode_requests(corro_ctx *ctx, const corro_reqdec_in *in, int mem, corro_reqdec_out *out, int pass) {
     if (!ctx || !in || !out) return fail(CORRO_E_INVALID, "NULL argument");
@@ -435,64 +412,49 @@ extern "C" int corro_decode_requests(corro_ctx *ctx, const corro_reqdec_in *in, 
     d.screen = screen ? 1u : 0u;
     d.book_nsites = S;
     d.ngaps = NG;
-    RD_TRY(wire_site_hash(ctx, &d.sites));
+    CORRO_TRY(wire_site_hash(ctx, &d.sites));
 
     size_t temp = 0;
-    RD_TRY(prim_inclusive_sum_u64(nullptr, &temp, nullptr, nullptr, std::max<uint64_t>(F, 1), s));
+    CORRO_TRY(prim_inclusive_sum_u64(nullptr, &temp, nullptr, nullptr, std::max<uint64_t>(F, 1), s));
     temp += 256;
-    const size_t stage = host ? al(in->len + 16) + al((F + 1) * 8) + al(S + 1) + al((S + 1) * 8) * 2 + 2 * al(NG * 8 + 8) : 0;
-    RD_TRY(ctx->d_reqdec[0].ensure(256 + al(F * 4 + 4) + 4 * al(F * 8 + 8) + 4 * al((F + 1) * 8) + al(temp) + stage));
-    Carver c0{ctx->d_reqdec[0].as<uint8_t>()};
-    d.misc = c0.take<unsigned long long>(32);
-    d.status = c0.take<int32_t>(F + 1);
-    d.c_pair = c0.take<uint64_t>(F + 1);
-    d.c_need = c0.take<uint64_t>(F + 1);
-    d.c_seq = c0.take<uint64_t>(F + 1);
-    d.c_ent = c0.take<uint64_t>(F + 1);
-    d.o_pair = c0.take<uint64_t>(F + 1);
-    d.o_need = c0.take<uint64_t>(F + 1);
-    d.o_seq = c0.take<uint64_t>(F + 1);
-    d.o_ent = c0.take<uint64_t>(F + 1);
-    void *tmp = c0.take<uint8_t>(temp);
-    if (host) {
-        bool ok = true;
-        auto up = [&](const void *src, size_t b, size_t room) -> const void * {
-            uint8_t *dst = c0.take<uint8_t>(room);
-            if (b && hipMemcpyAsync(dst, src, b, hipMemcpyHostToDevice, s) != hipSuccess) ok = false;
-            return dst;
-        };
-        d.buf = (const uint8_t *)up(in->buf, in->len, in->len + 16);
-        d.frame_off = (const uint64_t *)up(in->frame_off, (F + 1) * 8, (F + 1) * 8);
-        if (screen) {
-            d.book_known = (const uint8_t *)up(in->book_known, S, S + 1);
-            d.book_max = (const int64_t *)up(in->book_max, S * 8ull, (S + 1) * 8ull);
-            d.gap_off = (const uint64_t *)up(in->gap_off, (S + 1) * 8ull, (S + 1) * 8ull);
-            d.gap_start = (const uint64_t *)up(in->gap_start, NG * 8, NG * 8 + 8);
-            d.gap_end = (const uint64_t *)up(in->gap_end, NG * 8, NG * 8 + 8);
+    Stager st{s, host};
+    void *tmp = nullptr;
+    CORRO_TRY(carve(ctx->d_reqdec[0], [&](Carver &c) {
+        d.misc = c.take<unsigned long long>(32);
+        d.status = c.take<int32_t>(F + 1);
+        d.c_pair = c.take<uint64_t>(F + 1);
+        d.c_need = c.take<uint64_t>(F + 1);
+        d.c_seq = c.take<uint64_t>(F + 1);
+        d.c_ent = c.take<uint64_t>(F + 1);
+        d.o_pair = c.take<uint64_t>(F + 1);
+        d.o_need = c.take<uint64_t>(F + 1);
+        d.o_seq = c.take<uint64_t>(F + 1);
+        d.o_ent = c.take<uint64_t>(F + 1);
+        tmp = c.take<uint8_t>(temp);
+        d.buf = c.up(in->buf, in->len, in->len + 16);
+        d.frame_off = c.up(in->frame_off, (F + 1) * 8, (F + 1) * 8);
+        if (screen) {                              // (without gap_off no book array is given)
+            d.book_known = c.up(in->book_known, S, S + 1);
+            d.book_max = c.up(in->book_max, S * 8ull, (S + 1) * 8ull);
+            d.gap_off = c.up(in->gap_off, (S + 1) * 8ull, (S + 1) * 8ull);
+            d.gap_start = c.up(in->gap_start, NG * 8, NG * 8 + 8);
+            d.gap_end = c.up(in->gap_end, NG * 8, NG * 8 + 8);
         }
-        if (!ok) return fail(CORRO_E_DEVICE, "upload of the request frames failed");
-    } else {
-        d.buf = in->buf;
-        d.frame_off = in->frame_off;
-        d.book_known = in->book_known;
-        d.book_max = in->book_max;
-        d.gap_off = in->gap_off;
-        d.gap_start = in->gap_start;
-        d.gap_end = in->gap_end;
-    }
+    }, &st));
+    if (!st.ok) return fail(CORRO_E_DEVICE, "upload of the request frames failed");
     CORRO_HIP_TRY(hipMemsetAsync(d.misc, 0, 256, s));
     for (uint64_t *o : {d.o_pair, d.o_need, d.o_seq, d.o_ent}) CORRO_HIP_TRY(hipMemsetAsync(o, 0, 8, s));
-    RD_LAUNCH(k_rd_check, std::max<uint64_t>(F, screen ? std::max<uint64_t>(S, NG) : 0) + 1, d);
+    CORRO_LAUNCH(k_rd_check, grid_for(std::max<uint64_t>(F, screen ? std::max<uint64_t>(S, NG) : 0) + 1), d);
     if (F) {
-        RD_LAUNCH(k_rd_count, F, d);
+        CORRO_LAUNCH(k_rd_count, grid_for(F), d);
         const uint64_t *cs[4] = {d.c_pair, d.c_need, d.c_seq, d.c_ent};
         uint64_t *os[4] = {d.o_pair, d.o_need, d.o_seq, d.o_ent};
         for (int k = 0; k < 4; k++) {
             size_t t = temp;
-            RD_TRY(prim_inclusive_sum_u64(tmp, &t, cs[k], os[k] + 1, F, s));
+            CORRO_TRY(prim_inclusive_sum_u64(tmp, &t, cs[k], os[k] + 1, F, s));
         }
     }
-    RD_LAUNCH(k_rd_totals, 1, d);
+    CORRO_LAUNCH(k_rd_totals, dim3(1), d);
     unsigned long long misc[5] = {0, 0, 0, 0, 0};
     CORRO_HIP_TRY(hipMemcpyAsync(misc, d.misc, sizeof(misc), hipMemcpyDeviceToHost, s));
     CORRO_HIP_TRY(hipStreamSynchronize(s));
@@ -513,58 +475,50 @@ extern "C" int corro_decode_requests(corro_ctx *ctx, const corro_reqdec_in *in, 
     if (misc[1] != NP || misc[2] != NT || misc[3] != NQ || misc[4] != NE)
         return fail(CORRO_E_INVALID, "sizes differ from pass 0");
     corro_reqdec_out o = *out;
-    if (host) {
-        RD_TRY(ctx->d_reqdec[1].ensure(al(NP * 16 + 16) + al(NP * 4 + 4) + al((NP + 1) * 8) + 2 * al(NT + 1) + al(NT * 4 + 4) +
-                                       5 * al((NT + 1) * 8) + 2 * al(NQ * 8 + 8) + 3 * al(NE * 4 + 4) + 3 * al(NE * 8 + 8)));
-        Carver c1{ctx->d_reqdec[1].as<uint8_t>()};
-        o.pair_actor = c1.take<uint8_t>(NP * 16 + 16);
-        o.pair_site = c1.take<uint32_t>(NP + 1);
-        o.pair_need_off = c1.take<uint64_t>(NP + 1);
-        o.kind = c1.take<uint8_t>(NT + 1);
-        o.need_keep = c1.take<uint8_t>(NT + 1);
-        o.need_site = c1.take<uint32_t>(NT + 1);
-        o.start = c1.take<uint64_t>(NT + 1);
-        o.end = c1.take<uint64_t>(NT + 1);
-        o.sr_off = c1.take<uint64_t>(NT + 1);
-        o.sr_n = c1.take<uint64_t>(NT + 1);
-        o.need_ent_off = c1.take<uint64_t>(NT + 1);
-        o.s_start = c1.take<uint64_t>(NQ + 1);
-        o.s_end = c1.take<uint64_t>(NQ + 1);
-        o.ent_site = c1.take<uint32_t>(NE + 1);
-        o.ent_seq_start = c1.take<uint32_t>(NE + 1);
-        o.ent_seq_end = c1.take<uint32_t>(NE + 1);
-        o.ent_start = c1.take<uint64_t>(NE + 1);
-        o.ent_end = c1.take<uint64_t>(NE + 1);
-        o.ent_need = c1.take<uint64_t>(NE + 1);
-    }
+    if (host)
+        CORRO_TRY(carve(ctx->d_reqdec[1], [&](Carver &c) {
+            o.pair_actor = c.take<uint8_t>(NP * 16 + 16);
+            o.pair_site = c.take<uint32_t>(NP + 1);
+            o.pair_need_off = c.take<uint64_t>(NP + 1);
+            o.kind = c.take<uint8_t>(NT + 1);
+            o.need_keep = c.take<uint8_t>(NT + 1);
+            o.need_site = c.take<uint32_t>(NT + 1);
+            o.start = c.take<uint64_t>(NT + 1);
+            o.end = c.take<uint64_t>(NT + 1);
+            o.sr_off = c.take<uint64_t>(NT + 1);
+            o.sr_n = c.take<uint64_t>(NT + 1);
+            o.need_ent_off = c.take<uint64_t>(NT + 1);
+            o.s_start = c.take<uint64_t>(NQ + 1);
+            o.s_end = c.take<uint64_t>(NQ + 1);
+            o.ent_site = c.take<uint32_t>(NE + 1);
+            o.ent_seq_start = c.take<uint32_t>(NE + 1);
+            o.ent_seq_end = c.take<uint32_t>(NE + 1);
+            o.ent_start = c.take<uint64_t>(NE + 1);
+            o.ent_end = c.take<uint64_t>(NE + 1);
+            o.ent_need = c.take<uint64_t>(NE + 1);
+        }));
     d.out = o;
-    RD_LAUNCH(k_rd_fill, F + 1, d);
-    if (host) {
-        bool ok = true;
-        auto down = [&](void *dst, const void *src, size_t b) {
-            if (b && hipMemcpyAsync(dst, src, b, hipMemcpyDeviceToHost, s) != hipSuccess) ok = false;
-        };
-        down(out->pair_actor, o.pair_actor, NP * 16);
-        down(out->pair_site, o.pair_site, NP * 4);
-        down(out->pair_need_off, o.pair_need_off, (NP + 1) * 8);
-        down(out->kind, o.kind, NT);
-        down(out->need_keep, o.need_keep, NT);
-        down(out->need_site, o.need_site, NT * 4);
-        down(out->start, o.start, NT * 8);
-        down(out->end, o.end, NT * 8);
-        down(out->sr_off, o.sr_off, NT * 8);
-        down(out->sr_n, o.sr_n, NT * 8);
-        down(out->need_ent_off, o.need_ent_off, (NT + 1) * 8);
-        down(out->s_start, o.s_start, NQ * 8);
-        down(out->s_end, o.s_end, NQ * 8);
-        down(out->ent_site, o.ent_site, NE * 4);
-        down(out->ent_seq_start, o.ent_seq_start, NE * 4);
-        down(out->ent_seq_end, o.ent_seq_end, NE * 4);
-        down(out->ent_start, o.ent_start, NE * 8);
-        down(out->ent_end, o.ent_end, NE * 8);
-        down(out->ent_need, o.ent_need, NE * 8);
-        if (!ok) return fail(CORRO_E_DEVICE, "download of the decoded requests failed");
-    }
+    CORRO_LAUNCH(k_rd_fill, grid_for(F + 1), d);
+    st.down(out->pair_actor, o.pair_actor, NP * 16);
+    st.down(out->pair_site, o.pair_site, NP * 4);
+    st.down(out->pair_need_off, o.pair_need_off, (NP + 1) * 8);
+    st.down(out->kind, o.kind, NT);
+    st.down(out->need_keep, o.need_keep, NT);
+    st.down(out->need_site, o.need_site, NT * 4);
+    st.down(out->start, o.start, NT * 8);
+    st.down(out->end, o.end, NT * 8);
+    st.down(out->sr_off, o.sr_off, NT * 8);
+    st.down(out->sr_n, o.sr_n, NT * 8);
+    st.down(out->need_ent_off, o.need_ent_off, (NT + 1) * 8);
+    st.down(out->s_start, o.s_start, NQ * 8);
+    st.down(out->s_end, o.s_end, NQ * 8);
+    st.down(out->ent_site, o.ent_site, NE * 4);
+    st.down(out->ent_seq_start, o.ent_seq_start, NE * 4);
+    st.down(out->ent_seq_end, o.ent_seq_end, NE * 4);
+    st.down(out->ent_start, o.ent_start, NE * 8);
+    st.down(out->ent_end, o.ent_end, NE * 8);
+    st.down(out->ent_need, o.ent_need, NE * 8);
+    if (!st.ok) return fail(CORRO_E_DEVICE, "download of the decoded requests failed");
     CORRO_HIP_TRY(hipStreamSynchronize(s));
     return CORRO_OK;
 }
@@ -599,50 +553,41 @@ extern "C" int corro_need_spans(corro_ctx *ctx, const corro_spans_in *in, int me
     SpDev d{};
     d.in = *in;
     size_t temp = 0;
-    RD_TRY(prim_inclusive_sum_u64(nullptr, &temp, nullptr, nullptr, std::max<uint64_t>(T, 1), s));
+    CORRO_TRY(prim_inclusive_sum_u64(nullptr, &temp, nullptr, nullptr, std::max<uint64_t>(T, 1), s));
     temp += 256;
-    const size_t stage = host ? 2 * al(T + 1) + al(T * 4 + 4) + 3 * al((T + 1) * 8) + 2 * al(Q * 8 + 8) + al((E + 1) * 8) +
-                                    5 * al(G * 8 + 8)
-                              : 0;
-    RD_TRY(ctx->d_reqdec[0].ensure(256 + al(T * 8 + 8) + al((T + 1) * 8) + al(T + 1) + al(temp) + stage));
-    Carver c0{ctx->d_reqdec[0].as<uint8_t>()};
-    d.misc = c0.take<unsigned long long>(32);
-    d.cnt = c0.take<uint64_t>(T + 1);
-    d.off = c0.take<uint64_t>(T + 1);
-    d.in_state = c0.take<uint8_t>(T + 1);
-    void *tmp = c0.take<uint8_t>(temp);
-    if (host) {
-        bool ok = true;
-        auto up = [&](const void *src, size_t b, size_t room) -> const void * {
-            uint8_t *dst = c0.take<uint8_t>(room);
-            if (b && hipMemcpyAsync(dst, src, b, hipMemcpyHostToDevice, s) != hipSuccess) ok = false;
-            return dst;
-        };
-        d.in.kind = (const uint8_t *)up(in->kind, T, T + 1);
-        d.in.need_keep = (const uint8_t *)up(in->need_keep, T, T + 1);
-        d.in.need_site = (const uint32_t *)up(in->need_site, T * 4, T * 4 + 4);
-        d.in.sr_off = (const uint64_t *)up(in->sr_off, T * 8, (T + 1) * 8);
-        d.in.sr_n = (const uint64_t *)up(in->sr_n, T * 8, (T + 1) * 8);
-        d.in.need_ent_off = (const uint64_t *)up(in->need_ent_off, (T + 1) * 8, (T + 1) * 8);
-        d.in.s_start = (const uint64_t *)up(in->s_start, Q * 8, Q * 8 + 8);
-        d.in.s_end = (const uint64_t *)up(in->s_end, Q * 8, Q * 8 + 8);
-        d.in.grp_off = (const uint64_t *)up(in->grp_off, (E + 1) * 8, (E + 1) * 8);
-        d.in.version = (const int64_t *)up(in->version, G * 8, G * 8 + 8);
-        d.in.last_seq = (const uint64_t *)up(in->last_seq, G * 8, G * 8 + 8);
-        d.in.ts = (const uint64_t *)up(in->ts, G * 8, G * 8 + 8);
-        d.in.grp_row_off = (const uint64_t *)up(in->grp_row_off, G * 8, G * 8 + 8);
-        d.in.grp_rows = (const uint64_t *)up(in->grp_rows, G * 8, G * 8 + 8);
-        if (!ok) return fail(CORRO_E_DEVICE, "upload of the needs failed");
-    }
+    Stager st{s, host};
+    void *tmp = nullptr;
+    CORRO_TRY(carve(ctx->d_reqdec[0], [&](Carver &c) {
+        d.misc = c.take<unsigned long long>(32);
+        d.cnt = c.take<uint64_t>(T + 1);
+        d.off = c.take<uint64_t>(T + 1);
+        d.in_state = c.take<uint8_t>(T + 1);
+        tmp = c.take<uint8_t>(temp);
+        d.in.kind = c.up(in->kind, T, T + 1);
+        d.in.need_keep = c.up(in->need_keep, T, T + 1);
+        d.in.need_site = c.up(in->need_site, T * 4, T * 4 + 4);
+        d.in.sr_off = c.up(in->sr_off, T * 8, (T + 1) * 8);
+        d.in.sr_n = c.up(in->sr_n, T * 8, (T + 1) * 8);
+        d.in.need_ent_off = c.up(in->need_ent_off, (T + 1) * 8, (T + 1) * 8);
+        d.in.s_start = c.up(in->s_start, Q * 8, Q * 8 + 8);
+        d.in.s_end = c.up(in->s_end, Q * 8, Q * 8 + 8);
+        d.in.grp_off = c.up(in->grp_off, (E + 1) * 8, (E + 1) * 8);
+        d.in.version = c.up(in->version, G * 8, G * 8 + 8);
+        d.in.last_seq = c.up(in->last_seq, G * 8, G * 8 + 8);
+        d.in.ts = c.up(in->ts, G * 8, G * 8 + 8);
+        d.in.grp_row_off = c.up(in->grp_row_off, G * 8, G * 8 + 8);
+        d.in.grp_rows = c.up(in->grp_rows, G * 8, G * 8 + 8);
+    }, &st));
+    if (!st.ok) return fail(CORRO_E_DEVICE, "upload of the needs failed");
     CORRO_HIP_TRY(hipMemsetAsync(d.misc, 0, 256, s));
     CORRO_HIP_TRY(hipMemsetAsync(d.off, 0, 8, s));
-    RD_LAUNCH(k_sp_check, std::max(T, E) + 1, d);
+    CORRO_LAUNCH(k_sp_check, grid_for(std::max(T, E) + 1), d);
     if (T) {
-        RD_LAUNCH(k_sp_count, T, d);
+        CORRO_LAUNCH(k_sp_count, grid_for(T), d);
         size_t t = temp;
-        RD_TRY(prim_inclusive_sum_u64(tmp, &t, d.cnt, d.off + 1, T, s));
+        CORRO_TRY(prim_inclusive_sum_u64(tmp, &t, d.cnt, d.off + 1, T, s));
     }
-    RD_LAUNCH(k_sp_total, 1, d);
+    CORRO_LAUNCH(k_sp_total, dim3(1), d);
     unsigned long long misc[2] = {0, 0};
     CORRO_HIP_TRY(hipMemcpyAsync(misc, d.misc, sizeof(misc), hipMemcpyDeviceToHost, s));
     CORRO_HIP_TRY(hipStreamSynchronize(s));
@@ -660,35 +605,28 @@ extern "C" int corro_need_spans(corro_ctx *ctx, const corro_spans_in *in, int me
     if (misc[1] != N) return fail(CORRO_E_INVALID, "sizes differ from pass 0");
     if (N == 0) return CORRO_OK;
     corro_spans_out o = *out;
-    if (host) {
-        RD_TRY(ctx->d_reqdec[1].ensure(al(N * 4) + 7 * al(N * 8)));
-        Carver c1{ctx->d_reqdec[1].as<uint8_t>()};
-        o.site = c1.take<uint32_t>(N);
-        o.version = c1.take<int64_t>(N);
-        o.last_seq = c1.take<uint64_t>(N);
-        o.ts = c1.take<uint64_t>(N);
-        o.seq_start = c1.take<uint64_t>(N);
-        o.seq_end = c1.take<uint64_t>(N);
-        o.row_off = c1.take<uint64_t>(N);
-        o.row_count = c1.take<uint64_t>(N);
-    }
+    if (host)
+        CORRO_TRY(carve(ctx->d_reqdec[1], [&](Carver &c) {
+            o.site = c.take<uint32_t>(N);
+            o.version = c.take<int64_t>(N);
+            o.last_seq = c.take<uint64_t>(N);
+            o.ts = c.take<uint64_t>(N);
+            o.seq_start = c.take<uint64_t>(N);
+            o.seq_end = c.take<uint64_t>(N);
+            o.row_off = c.take<uint64_t>(N);
+            o.row_count = c.take<uint64_t>(N);
+        }));
     d.out = o;
-    RD_LAUNCH(k_sp_fill, N, d, N);
-    if (host) {
-        bool ok = true;
-        auto down = [&](void *dst, const void *src, size_t b) {
-            if (hipMemcpyAsync(dst, src, b, hipMemcpyDeviceToHost, s) != hipSuccess) ok = false;
-        };
-        down(out->site, o.site, N * 4);
-        down(out->version, o.version, N * 8);
-        down(out->last_seq, o.last_seq, N * 8);
-        down(out->ts, o.ts, N * 8);
-        down(out->seq_start, o.seq_start, N * 8);
-        down(out->seq_end, o.seq_end, N * 8);
-        down(out->row_off, o.row_off, N * 8);
-        down(out->row_count, o.row_count, N * 8);
-        if (!ok) return fail(CORRO_E_DEVICE, "download of the spans failed");
-    }
+    CORRO_LAUNCH(k_sp_fill, grid_for(N), d, N);
+    st.down(out->site, o.site, N * 4);
+    st.down(out->version, o.version, N * 8);
+    st.down(out->last_seq, o.last_seq, N * 8);
+    st.down(out->ts, o.ts, N * 8);
+    st.down(out->seq_start, o.seq_start, N * 8);
+    st.down(out->seq_end, o.seq_end, N * 8);
+    st.down(out->row_off, o.row_off, N * 8);
+    st.down(out->row_count, o.row_count, N * 8);
+    if (!st.ok) return fail(CORRO_E_DEVICE, "download of the spans failed");
     CORRO_HIP_TRY(hipStreamSynchronize(s));
     return CORRO_OK;
 }

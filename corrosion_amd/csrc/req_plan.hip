@@ -39,10 +39,9 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstring>
-#include <vector>
 
 #include "internal.h"
+#include "scratch.h"
 
 namespace corro {
 int ovf_sort_pairs(void *temp, size_t *temp_bytes, const uint64_t *ki, uint64_t *ko, const uint32_t *vi,
@@ -424,20 +423,7 @@ __global__ void __launch_bounds__(64) k_req_write(ReqDev d) {
     }
 }
 
-size_t al(size_t b) { return ((b + 255) / 256) * 256; }
-
 uint32_t bits_for(uint64_t maxval) { return maxval ? 64u - (uint32_t)__builtin_clzll(maxval) : 1u; }
-
-struct Carver {
-    uint8_t *q = nullptr;
-    template <class T> T *take(size_t count) {
-        uint8_t *r = q;
-        q += al(count * sizeof(T));
-        return reinterpret_cast<T *>(r);
-    }
-};
-
-dim3 grid_for(uint64_t n, uint32_t block = 256) { return dim3((uint32_t)((n + block - 1) / block)); }
 
 // rocPRIM temp bytes of the primitives run over `n` elements
 int temp_for(uint64_t n, hipStream_t s, size_t *out) {
@@ -470,19 +456,6 @@ int report(uint64_t err) {
 }  // namespace corro
 
 using namespace corro;
-
-#define REQ_LAUNCH(kernel, count, ...)                                                         \
-    do {                                                                                       \
-        if ((count) > 0) {                                                                     \
-            hipLaunchKernelGGL(kernel, grid_for(count), dim3(256), 0, s, __VA_ARGS__);         \
-            CORRO_HIP_TRY(hipGetLastError());                                                  \
-        }                                                                                      \
-    } while (0)
-#define REQ_TRY(x)                       \
-    do {                                 \
-        int rc_ = (x);                   \
-        if (rc_ != CORRO_OK) return rc_; \
-    } while (0)
 
 extern "C" int corro_plan_requests(corro_ctx *ctx, const corro_request_in *in, int mem, corro_requests *out, int pass) {
     if (!ctx || !in || !out) return fail(CORRO_E_INVALID, "NULL argument");
@@ -527,114 +500,90 @@ extern "C" int corro_plan_requests(corro_ctx *ctx, const corro_request_in *in, i
 
     // ---- level 0: inputs, per need, per group
     size_t temp0 = 0;
-    REQ_TRY(temp_for(T, s, &temp0));
-    const size_t stage0 = host ? al(n * 4) + al((n + 1) * 8) + al(T) + 4 * al(T * 8) + 2 * al(Ts * 8) + al((G + 1) * 8) + al(G * 8)
-                               : 0;
-    REQ_TRY(ctx->d_req[0].ensure(al(nsites * 16 + 16) + 256 + al(T * 8) + al((T + 1) * 8) + 2 * al(T * 4) + al((G + 1) * 4) +
-                                 al(G * 4) + al(temp0) + stage0));
-    Carver c0{ctx->d_req[0].as<uint8_t>()};
-    {
-        uint8_t *ds = c0.take<uint8_t>(nsites * 16 + 16);
-        std::vector<uint8_t> hs(nsites * 16 + 16, 0);
-        for (size_t i = 0; i < nsites; i++) std::memcpy(hs.data() + 16 * i, ctx->sites[i].data(), 16);
-        CORRO_HIP_TRY(hipMemcpyAsync(ds, hs.data(), hs.size(), hipMemcpyHostToDevice, s));
-        CORRO_HIP_TRY(hipStreamSynchronize(s));   // hs leaves scope
-        d.sites = ds;
-    }
-    d.misc = c0.take<unsigned long long>(32);
-    d.n_cnt = c0.take<uint64_t>(T);
-    d.item_off = c0.take<uint64_t>(T + 1);
-    d.n_ent = c0.take<uint32_t>(T);
-    d.n_grp = c0.take<uint32_t>(T);
-    d.g_lo = c0.take<uint32_t>(G + 1);
-    d.g_first = c0.take<uint32_t>(G);
-    void *tmp0 = c0.take<uint8_t>(temp0);
-    if (host) {
-        bool ok = true;
-        auto up = [&](const void *src, size_t b) -> const void * {
-            uint8_t *dst = c0.take<uint8_t>(b);
-            if (b && hipMemcpyAsync(dst, src, b, hipMemcpyHostToDevice, s) != hipSuccess) ok = false;
-            return dst;
-        };
-        d.site = (const uint32_t *)up(in->site, n * 4);
-        d.need_off = (const uint64_t *)up(in->need_off, (n + 1) * 8);
-        d.kind = (const uint8_t *)up(in->kind, T);
-        d.start = (const uint64_t *)up(in->start, T * 8);
-        d.end = (const uint64_t *)up(in->end, T * 8);
-        d.sr_off = (const uint64_t *)up(in->sr_off, T * 8);
-        d.sr_n = (const uint64_t *)up(in->sr_n, T * 8);
-        d.s_start = (const uint64_t *)up(in->s_start, Ts * 8);
-        d.s_end = (const uint64_t *)up(in->s_end, Ts * 8);
-        d.geo = (const uint64_t *)up(in->grp_ent_off, (G + 1) * 8);
-        d.ses = (const uint64_t *)up(in->grp_session, G * 8);
-        if (!ok) return fail(CORRO_E_DEVICE, "upload of the needs failed");
-    } else {
-        d.site = in->site;
-        d.need_off = in->need_off;
-        d.kind = in->kind;
-        d.start = in->start;
-        d.end = in->end;
-        d.sr_off = in->sr_off;
-        d.sr_n = in->sr_n;
-        d.s_start = in->s_start;
-        d.s_end = in->s_end;
-        d.geo = in->grp_ent_off;
-        d.ses = in->grp_session;
-    }
+    CORRO_TRY(temp_for(T, s, &temp0));
+    Stager st{s, host};
+    void *tmp0 = nullptr;
+    uint8_t *dsites = nullptr;
+    CORRO_TRY(carve(ctx->d_req[0], [&](Carver &c) {
+        d.sites = dsites = c.take<uint8_t>(nsites * 16 + 16);
+        d.misc = c.take<unsigned long long>(32);
+        d.n_cnt = c.take<uint64_t>(T);
+        d.item_off = c.take<uint64_t>(T + 1);
+        d.n_ent = c.take<uint32_t>(T);
+        d.n_grp = c.take<uint32_t>(T);
+        d.g_lo = c.take<uint32_t>(G + 1);
+        d.g_first = c.take<uint32_t>(G);
+        tmp0 = c.take<uint8_t>(temp0);
+        d.site = c.up(in->site, n * 4, n * 4);
+        d.need_off = c.up(in->need_off, (n + 1) * 8, (n + 1) * 8);
+        d.kind = c.up(in->kind, T, T);
+        d.start = c.up(in->start, T * 8, T * 8);
+        d.end = c.up(in->end, T * 8, T * 8);
+        d.sr_off = c.up(in->sr_off, T * 8, T * 8);
+        d.sr_n = c.up(in->sr_n, T * 8, T * 8);
+        d.s_start = c.up(in->s_start, Ts * 8, Ts * 8);
+        d.s_end = c.up(in->s_end, Ts * 8, Ts * 8);
+        d.geo = c.up(in->grp_ent_off, (G + 1) * 8, (G + 1) * 8);
+        d.ses = c.up(in->grp_session, G * 8, G * 8);
+    }, &st));
+    if (!st.ok) return fail(CORRO_E_DEVICE, "upload of the needs failed");
+    CORRO_TRY(upload_site_table(ctx, dsites, s));
     CORRO_HIP_TRY(hipMemsetAsync(d.misc, 0, 256, s));
     CORRO_HIP_TRY(hipMemsetAsync(d.item_off, 0, 8, s));
-    REQ_LAUNCH(k_req_check, std::max(n, G) + 1, d);
-    REQ_LAUNCH(k_req_need, T, d);
+    CORRO_LAUNCH(k_req_check, grid_for(std::max(n, G) + 1), d);
+    if (T) CORRO_LAUNCH(k_req_need, grid_for(T), d);
     if (T) {
         size_t t = temp0;
-        REQ_TRY(prim_inclusive_sum_u64(tmp0, &t, d.n_cnt, d.item_off + 1, T, s));
+        CORRO_TRY(prim_inclusive_sum_u64(tmp0, &t, d.n_cnt, d.item_off + 1, T, s));
     }
     unsigned long long misc[3] = {0, 0, 0};
     uint64_t NI = 0;
     CORRO_HIP_TRY(hipMemcpyAsync(misc, d.misc, 24, hipMemcpyDeviceToHost, s));
     CORRO_HIP_TRY(hipMemcpyAsync(&NI, d.item_off + T, 8, hipMemcpyDeviceToHost, s));
     CORRO_HIP_TRY(hipStreamSynchronize(s));
-    REQ_TRY(report(misc[0]));
+    CORRO_TRY(report(misc[0]));
     if (NI > MAX32) return fail(CORRO_E_RANGE, "more than 2^32 - 1 request items in a call");
     d.NI = NI;
     const uint32_t cbits = bits_for(misc[1]), vbits = bits_for(misc[2]);
-    REQ_LAUNCH(k_req_group, G + 1, d);
+    CORRO_LAUNCH(k_req_group, grid_for(G + 1), d);
 
     // ---- level 1: items
     size_t temp1 = 0;
-    REQ_TRY(temp_for(NI + 1, s, &temp1));
-    REQ_TRY(ctx->d_req[1].ensure(2 * al(NI * 8) + 10 * al((NI + 1) * 4) + 5 * al((NI + 1) * 8) + al(temp1)));
-    Carver c1{ctx->d_req[1].as<uint8_t>()};
-    d.ikey = c1.take<uint64_t>(NI);
-    uint64_t *ikey2 = c1.take<uint64_t>(NI);
-    d.ival = c1.take<uint32_t>(NI + 1);
-    d.o_x = c1.take<uint32_t>(NI + 1);
-    d.xo = c1.take<uint32_t>(NI + 1);
-    d.o_t = c1.take<uint32_t>(NI + 1);
-    d.o_c = c1.take<uint32_t>(NI + 1);
-    d.rcnt = c1.take<uint32_t>(NI + 1);
-    d.pcnt = c1.take<uint32_t>(NI + 1);
-    d.poff = c1.take<uint32_t>(NI + 1);
-    d.has = c1.take<uint32_t>(NI + 1);
-    d.fexcl = c1.take<uint32_t>(NI + 1);
-    d.o_gs = c1.take<uint64_t>(NI + 1);
-    d.o_ver = c1.take<uint64_t>(NI + 1);
-    d.roff = c1.take<uint64_t>(NI + 1);
-    d.fsize = c1.take<uint64_t>(NI + 1);
-    d.boff = c1.take<uint64_t>(NI + 1);
-    void *tmp1 = c1.take<uint8_t>(temp1);
+    CORRO_TRY(temp_for(NI + 1, s, &temp1));
+    uint64_t *ikey2 = nullptr;
+    void *tmp1 = nullptr;
+    CORRO_TRY(carve(ctx->d_req[1], [&](Carver &c) {
+        d.ikey = c.take<uint64_t>(NI);
+        ikey2 = c.take<uint64_t>(NI);
+        d.ival = c.take<uint32_t>(NI + 1);
+        d.o_x = c.take<uint32_t>(NI + 1);
+        d.xo = c.take<uint32_t>(NI + 1);
+        d.o_t = c.take<uint32_t>(NI + 1);
+        d.o_c = c.take<uint32_t>(NI + 1);
+        d.rcnt = c.take<uint32_t>(NI + 1);
+        d.pcnt = c.take<uint32_t>(NI + 1);
+        d.poff = c.take<uint32_t>(NI + 1);
+        d.has = c.take<uint32_t>(NI + 1);
+        d.fexcl = c.take<uint32_t>(NI + 1);
+        d.o_gs = c.take<uint64_t>(NI + 1);
+        d.o_ver = c.take<uint64_t>(NI + 1);
+        d.roff = c.take<uint64_t>(NI + 1);
+        d.fsize = c.take<uint64_t>(NI + 1);
+        d.boff = c.take<uint64_t>(NI + 1);
+        tmp1 = c.take<uint8_t>(temp1);
+    }));
     CORRO_HIP_TRY(hipMemsetAsync(d.roff, 0, 8, s));
     CORRO_HIP_TRY(hipMemsetAsync(d.poff, 0, 4, s));
     CORRO_HIP_TRY(hipMemsetAsync(d.fexcl, 0, 4, s));
     CORRO_HIP_TRY(hipMemsetAsync(d.boff, 0, 8, s));
     uint64_t NR = 0;
     if (NI) {
-        REQ_LAUNCH(k_req_item, NI, d);
+        CORRO_LAUNCH(k_req_item, grid_for(NI), d);
         size_t t = temp1;
-        REQ_TRY(ovf_sort_pairs(tmp1, &t, d.ikey, ikey2, d.ival, d.o_x, (uint32_t)NI, 32 + d.gbits, s));
-        REQ_LAUNCH(k_req_ord, NI, d);
+        CORRO_TRY(ovf_sort_pairs(tmp1, &t, d.ikey, ikey2, d.ival, d.o_x, (uint32_t)NI, 32 + d.gbits, s));
+        CORRO_LAUNCH(k_req_ord, grid_for(NI), d);
         t = temp1;
-        REQ_TRY(prim_inclusive_scan_u32_u64(tmp1, &t, d.rcnt, d.roff + 1, NI, s));
+        CORRO_TRY(prim_inclusive_scan_u32_u64(tmp1, &t, d.rcnt, d.roff + 1, NI, s));
         CORRO_HIP_TRY(hipMemcpyAsync(&NR, d.roff + NI, 8, hipMemcpyDeviceToHost, s));
         CORRO_HIP_TRY(hipStreamSynchronize(s));
     }
@@ -644,37 +593,39 @@ extern "C" int corro_plan_requests(corro_ctx *ctx, const corro_request_in *in, i
     // ---- level 2: ranges and their endpoints
     const uint64_t NEP = 2 * NR;
     size_t temp2 = 0;
-    REQ_TRY(temp_for(NEP, s, &temp2));
-    REQ_TRY(ctx->d_req[2].ensure(2 * al(NR * 8) + al((NR + 1) * 8) + 2 * al(NR * 4) + 2 * al(NEP * 8) + 5 * al(NEP * 4) +
-                                 al(NEP) + al(temp2)));
-    Carver c2{ctx->d_req[2].as<uint8_t>()};
-    d.r_lo = c2.take<uint64_t>(NR);
-    d.r_hi1 = c2.take<uint64_t>(NR);
-    d.eoff = c2.take<uint64_t>(NR + 1);
-    d.r_o = c2.take<uint32_t>(NR);
-    d.ecnt = c2.take<uint32_t>(NR);
-    uint64_t *ek0 = c2.take<uint64_t>(NEP), *ek1 = c2.take<uint64_t>(NEP);
-    uint32_t *pm0 = c2.take<uint32_t>(NEP), *pm1 = c2.take<uint32_t>(NEP);
-    d.pt = c2.take<uint32_t>(NEP);
-    d.f_nc = c2.take<uint32_t>(NEP);
-    d.uid = c2.take<uint32_t>(NEP);
-    d.f_ng = c2.take<uint8_t>(NEP);
-    void *tmp2 = c2.take<uint8_t>(temp2);
+    CORRO_TRY(temp_for(NEP, s, &temp2));
+    uint64_t *ek0 = nullptr, *ek1 = nullptr;
+    uint32_t *pm0 = nullptr, *pm1 = nullptr;
+    void *tmp2 = nullptr;
+    CORRO_TRY(carve(ctx->d_req[2], [&](Carver &c) {
+        d.r_lo = c.take<uint64_t>(NR);
+        d.r_hi1 = c.take<uint64_t>(NR);
+        d.eoff = c.take<uint64_t>(NR + 1);
+        d.r_o = c.take<uint32_t>(NR);
+        d.ecnt = c.take<uint32_t>(NR);
+        ek0 = c.take<uint64_t>(NEP), ek1 = c.take<uint64_t>(NEP);
+        pm0 = c.take<uint32_t>(NEP), pm1 = c.take<uint32_t>(NEP);
+        d.pt = c.take<uint32_t>(NEP);
+        d.f_nc = c.take<uint32_t>(NEP);
+        d.uid = c.take<uint32_t>(NEP);
+        d.f_ng = c.take<uint8_t>(NEP);
+        tmp2 = c.take<uint8_t>(temp2);
+    }));
     uint64_t NU = 0, NE = 0;
     if (NR) {
-        REQ_LAUNCH(k_req_range, NR, d);
-        REQ_LAUNCH(k_req_iota, NEP, pm0, NEP);
+        CORRO_LAUNCH(k_req_range, grid_for(NR), d);
+        CORRO_LAUNCH(k_req_iota, grid_for(NEP), pm0, NEP);
         // three stable sorts, least significant key first: coordinate, version, (kind, session, site)
         const uint32_t lbits[3] = {cbits, vbits, 1 + d.gbits + d.sbits};
         for (int level = 0; level < 3; level++) {
-            REQ_LAUNCH(k_req_epkey, NEP, d, pm0, ek0, level);
+            CORRO_LAUNCH(k_req_epkey, grid_for(NEP), d, pm0, ek0, level);
             size_t t = temp2;
-            REQ_TRY(ovf_sort_pairs(tmp2, &t, ek0, ek1, pm0, pm1, (uint32_t)NEP, lbits[level], s));
+            CORRO_TRY(ovf_sort_pairs(tmp2, &t, ek0, ek1, pm0, pm1, (uint32_t)NEP, lbits[level], s));
             std::swap(pm0, pm1);
         }
-        REQ_LAUNCH(k_req_uniq, NEP, d, pm0);
+        CORRO_LAUNCH(k_req_uniq, grid_for(NEP), d, pm0);
         size_t t = temp2;
-        REQ_TRY(prim_inclusive_scan_u32(tmp2, &t, d.f_nc, d.uid, (uint32_t)NEP, s));
+        CORRO_TRY(prim_inclusive_scan_u32(tmp2, &t, d.f_nc, d.uid, (uint32_t)NEP, s));
         uint32_t nu32 = 0;
         CORRO_HIP_TRY(hipMemcpyAsync(&nu32, d.uid + NEP - 1, 4, hipMemcpyDeviceToHost, s));
         CORRO_HIP_TRY(hipStreamSynchronize(s));
@@ -684,45 +635,47 @@ extern "C" int corro_plan_requests(corro_ctx *ctx, const corro_request_in *in, i
 
     // ---- level 3: unique points (segments) and elements
     size_t temp3 = 0;
-    REQ_TRY(temp_for(NU, s, &temp3));
-    const size_t l3 = al((NU + 1) * 8) + al(NU + 1) + 5 * al(NU * 4) + al(temp3);
-    REQ_TRY(ctx->d_req[3].ensure(l3));
-    Carver c3{ctx->d_req[3].as<uint8_t>()};
-    d.ucoord = c3.take<uint64_t>(NU + 1);
-    d.ufirst = c3.take<uint8_t>(NU + 1);
-    d.win = c3.take<uint32_t>(NU);
-    d.psf = c3.take<uint32_t>(NU);
-    d.pef = c3.take<uint32_t>(NU);
-    d.psi = c3.take<uint32_t>(NU);
-    d.pei = c3.take<uint32_t>(NU);
-    void *tmp3 = c3.take<uint8_t>(temp3);
+    CORRO_TRY(temp_for(NU, s, &temp3));
+    void *tmp3 = nullptr;
+    CORRO_TRY(carve(ctx->d_req[3], [&](Carver &c) {
+        d.ucoord = c.take<uint64_t>(NU + 1);
+        d.ufirst = c.take<uint8_t>(NU + 1);
+        d.win = c.take<uint32_t>(NU);
+        d.psf = c.take<uint32_t>(NU);
+        d.pef = c.take<uint32_t>(NU);
+        d.psi = c.take<uint32_t>(NU);
+        d.pei = c.take<uint32_t>(NU);
+        tmp3 = c.take<uint8_t>(temp3);
+    }));
     uint64_t NP = 0;
     if (NR) {
-        REQ_LAUNCH(k_req_pts, NEP, d, pm0);
-        REQ_LAUNCH(k_req_ecnt, NR, d);
+        CORRO_LAUNCH(k_req_pts, grid_for(NEP), d, pm0);
+        CORRO_LAUNCH(k_req_ecnt, grid_for(NR), d);
         CORRO_HIP_TRY(hipMemsetAsync(d.eoff, 0, 8, s));
         size_t t = temp2;
-        REQ_TRY(prim_inclusive_scan_u32_u64(tmp2, &t, d.ecnt, d.eoff + 1, NR, s));
+        CORRO_TRY(prim_inclusive_scan_u32_u64(tmp2, &t, d.ecnt, d.eoff + 1, NR, s));
         CORRO_HIP_TRY(hipMemcpyAsync(&NE, d.eoff + NR, 8, hipMemcpyDeviceToHost, s));
         CORRO_HIP_TRY(hipStreamSynchronize(s));
         if (NE > MAX32) return fail(CORRO_E_RANGE, "more than 2^32 - 1 range segments to plan in a call");
         d.NE = NE;
         size_t temp4 = 0;
-        REQ_TRY(temp_for(NE, s, &temp4));
-        REQ_TRY(ctx->d_req[4].ensure(2 * al(NE * 8) + al(temp4)));
-        Carver c4{ctx->d_req[4].as<uint8_t>()};
-        uint64_t *el0 = c4.take<uint64_t>(NE), *el1 = c4.take<uint64_t>(NE);
-        void *tmp4 = c4.take<uint8_t>(temp4);
-        REQ_LAUNCH(k_req_elem, NE, d, el0);
+        CORRO_TRY(temp_for(NE, s, &temp4));
+        uint64_t *el0 = nullptr, *el1 = nullptr;
+        void *tmp4 = nullptr;
+        CORRO_TRY(carve(ctx->d_req[4], [&](Carver &c) {
+            el0 = c.take<uint64_t>(NE), el1 = c.take<uint64_t>(NE);
+            tmp4 = c.take<uint8_t>(temp4);
+        }));
+        if (NE) CORRO_LAUNCH(k_req_elem, grid_for(NE), d, el0);
         t = temp4;
-        REQ_TRY(prim_sort_keys_u64(tmp4, &t, el0, el1, (uint32_t)NE, 32 + bits_for(NU), s));
+        CORRO_TRY(prim_sort_keys_u64(tmp4, &t, el0, el1, (uint32_t)NE, 32 + bits_for(NU), s));
         CORRO_HIP_TRY(hipMemsetAsync(d.win, 0xFF, NU * 4, s));
-        REQ_LAUNCH(k_req_win, NE, d, el1);
-        REQ_LAUNCH(k_req_pflag, NU, d);
+        if (NE) CORRO_LAUNCH(k_req_win, grid_for(NE), d, el1);
+        if (NU) CORRO_LAUNCH(k_req_pflag, grid_for(NU), d);
         t = temp3;
-        REQ_TRY(prim_inclusive_scan_u32(tmp3, &t, d.psf, d.psi, (uint32_t)NU, s));
+        CORRO_TRY(prim_inclusive_scan_u32(tmp3, &t, d.psf, d.psi, (uint32_t)NU, s));
         t = temp3;
-        REQ_TRY(prim_inclusive_scan_u32(tmp3, &t, d.pef, d.pei, (uint32_t)NU, s));
+        CORRO_TRY(prim_inclusive_scan_u32(tmp3, &t, d.pef, d.pei, (uint32_t)NU, s));
         uint32_t np32 = 0;
         CORRO_HIP_TRY(hipMemcpyAsync(&np32, d.psi + NU - 1, 4, hipMemcpyDeviceToHost, s));
         CORRO_HIP_TRY(hipStreamSynchronize(s));
@@ -732,44 +685,46 @@ extern "C" int corro_plan_requests(corro_ctx *ctx, const corro_request_in *in, i
 
     // ---- level 4: pieces by item, frame sizes and offsets
     size_t temp5 = 0;
-    REQ_TRY(temp_for(NP, s, &temp5));
-    REQ_TRY(ctx->d_req[5].ensure(4 * al(NP * 8) + 2 * al(NP * 4) + al(temp5) + al(F * 4)));
-    Carver c5{ctx->d_req[5].as<uint8_t>()};
-    d.pkey = c5.take<uint64_t>(NP);
-    uint64_t *pkey2 = c5.take<uint64_t>(NP);
-    d.p_lo = c5.take<uint64_t>(NP);
-    d.p_hi = c5.take<uint64_t>(NP);
-    d.pval = c5.take<uint32_t>(NP);
-    d.sp = c5.take<uint32_t>(NP);
-    void *tmp5 = c5.take<uint8_t>(temp5);
-    d.f_o = c5.take<uint32_t>(F);
+    CORRO_TRY(temp_for(NP, s, &temp5));
+    uint64_t *pkey2 = nullptr;
+    void *tmp5 = nullptr;
+    CORRO_TRY(carve(ctx->d_req[5], [&](Carver &c) {
+        d.pkey = c.take<uint64_t>(NP);
+        pkey2 = c.take<uint64_t>(NP);
+        d.p_lo = c.take<uint64_t>(NP);
+        d.p_hi = c.take<uint64_t>(NP);
+        d.pval = c.take<uint32_t>(NP);
+        d.sp = c.take<uint32_t>(NP);
+        tmp5 = c.take<uint8_t>(temp5);
+        d.f_o = c.take<uint32_t>(F);
+    }));
     if (NP) {
-        REQ_LAUNCH(k_req_pieces, NU, d);
+        if (NU) CORRO_LAUNCH(k_req_pieces, grid_for(NU), d);
         size_t t = temp5;
-        REQ_TRY(ovf_sort_pairs(tmp5, &t, d.pkey, pkey2, d.pval, d.sp, (uint32_t)NP, bits_for(NI), s));
+        CORRO_TRY(ovf_sort_pairs(tmp5, &t, d.pkey, pkey2, d.pval, d.sp, (uint32_t)NP, bits_for(NI), s));
     }
     uint64_t tot[2] = {0, 0};
     if (NI) {
         size_t t = temp1;
-        REQ_TRY(prim_inclusive_scan_u32(tmp1, &t, d.pcnt, d.poff + 1, (uint32_t)NI, s));
-        REQ_LAUNCH(k_req_fsize, NI, d);
+        CORRO_TRY(prim_inclusive_scan_u32(tmp1, &t, d.pcnt, d.poff + 1, (uint32_t)NI, s));
+        CORRO_LAUNCH(k_req_fsize, grid_for(NI), d);
         t = temp1;
-        REQ_TRY(prim_inclusive_scan_u32(tmp1, &t, d.has, d.fexcl + 1, (uint32_t)NI, s));
+        CORRO_TRY(prim_inclusive_scan_u32(tmp1, &t, d.has, d.fexcl + 1, (uint32_t)NI, s));
         t = temp1;
-        REQ_TRY(prim_inclusive_sum_u64(tmp1, &t, d.fsize, d.boff + 1, NI, s));
+        CORRO_TRY(prim_inclusive_sum_u64(tmp1, &t, d.fsize, d.boff + 1, NI, s));
         uint32_t nf32 = 0;
         CORRO_HIP_TRY(hipMemcpyAsync(misc, d.misc, 8, hipMemcpyDeviceToHost, s));
         CORRO_HIP_TRY(hipMemcpyAsync(&nf32, d.fexcl + NI, 4, hipMemcpyDeviceToHost, s));
         CORRO_HIP_TRY(hipMemcpyAsync(&tot[1], d.boff + NI, 8, hipMemcpyDeviceToHost, s));
         CORRO_HIP_TRY(hipStreamSynchronize(s));
         tot[0] = nf32;
-        REQ_TRY(report(misc[0]));
+        CORRO_TRY(report(misc[0]));
     }
     if (pass == 0) {
         // group g's frames: [fexcl[g_lo[g]], fexcl[g_lo[g + 1]])
-        REQ_TRY(ctx->d_req[6].ensure(al((G + 1) * 8)));
+        CORRO_TRY(ctx->d_req[6].ensure((G + 1) * 8));
         d.grp_frame_off = host ? ctx->d_req[6].as<uint64_t>() : out->grp_frame_off;
-        REQ_LAUNCH(k_req_goff, G + 1, d);
+        CORRO_LAUNCH(k_req_goff, grid_for(G + 1), d);
         if (host) CORRO_HIP_TRY(hipMemcpyAsync(out->grp_frame_off, d.grp_frame_off, (G + 1) * 8, back, s));
         CORRO_HIP_TRY(hipStreamSynchronize(s));
         out->nframes = tot[0];
@@ -779,22 +734,20 @@ extern "C" int corro_plan_requests(corro_ctx *ctx, const corro_request_in *in, i
     if (tot[0] != F || tot[1] != NB) return fail(CORRO_E_INVALID, "sizes differ from pass 0");
     d.NF = F;
     d.NB = NB;
-    if (host) {
-        REQ_TRY(ctx->d_req[6].ensure(al(NB + 16) + al((F + 1) * 8) + al(F * 8) + 2 * al(F * 4)));
-        Carver c6{ctx->d_req[6].as<uint8_t>()};
-        d.buf = c6.take<uint8_t>(NB + 16);
-        d.frame_off = c6.take<uint64_t>(F + 1);
-        d.frame_entry = c6.take<uint64_t>(F);
-        d.frame_round = c6.take<uint32_t>(F);
-        d.frame_needs = c6.take<uint32_t>(F);
-    } else {
-        d.buf = out->buf;
-        d.frame_off = out->frame_off;
-        d.frame_entry = out->frame_entry;
-        d.frame_round = out->frame_round;
-        d.frame_needs = out->frame_needs;
-    }
-    REQ_LAUNCH(k_req_ftab, std::max<uint64_t>(NI, 1), d);
+    d.buf = out->buf;
+    d.frame_off = out->frame_off;
+    d.frame_entry = out->frame_entry;
+    d.frame_round = out->frame_round;
+    d.frame_needs = out->frame_needs;
+    if (host)
+        CORRO_TRY(carve(ctx->d_req[6], [&](Carver &c) {
+            d.buf = c.take<uint8_t>(NB + 16);
+            d.frame_off = c.take<uint64_t>(F + 1);
+            d.frame_entry = c.take<uint64_t>(F);
+            d.frame_round = c.take<uint32_t>(F);
+            d.frame_needs = c.take<uint32_t>(F);
+        }));
+    CORRO_LAUNCH(k_req_ftab, grid_for(std::max<uint64_t>(NI, 1)), d);
     if (NB) {
         hipLaunchKernelGGL(k_req_write, dim3((uint32_t)((NB + REQ_TILE - 1) / REQ_TILE)), dim3(64), 0, s, d);
         CORRO_HIP_TRY(hipGetLastError());

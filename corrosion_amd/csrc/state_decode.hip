@@ -25,13 +25,14 @@
 //   k_sd_pcount, k_sd_fill   one wave per pair, lanes over theirs.heads, the five probes per entry without
 //                atomics; the fill repeats the count's probes and places every entry by a wave scan. No
 //                fill write passes the pair's window of the count.
-//   k_sd_fold    the check's flag words folded by one workgroup, and the totals next to them
+//   k_flag_fold  (scratch.h) the check's flag words folded by one workgroup, and the totals next to them
 // Workgroups share data only across kernel boundaries.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
 #include "internal.h"
+#include "scratch.h"
 
 namespace corro {
 int prim_inclusive_sum_u64(void *temp, size_t *temp_bytes, const uint64_t *in, uint64_t *out, uint64_t n, hipStream_t s);
@@ -82,11 +83,6 @@ __device__ inline uint32_t tab_size(uint32_t n) {
     return s;
 }
 __device__ inline uint32_t key_hash(uint64_t lo, uint64_t hi) { return (uint32_t)site_mix(lo ^ (hi * 0x9E3779B97F4A7C15ULL)); }
-
-__device__ inline void wg_flag(uint32_t *part, bool bad) {
-    const int any = __syncthreads_or(bad ? 1 : 0);
-    if (threadIdx.x == 0) part[blockIdx.x] = any ? 1u : 0u;
-}
 
 __global__ void k_sd_check(SdDev d) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -228,19 +224,6 @@ __global__ void k_sd_count(SdDev d) {
     d.c_pa[f] = fc.np;
     d.c_pv[f] = fc.npv;
     d.c_slot[f] = (uint64_t)tab_size(fc.nh) + tab_size((uint32_t)fc.nn) + tab_size((uint32_t)fc.np);
-}
-
-// One workgroup: misc[0] |= any flag word; misc[at + k] = *tot[k].
-struct Totals {
-    const uint64_t *p[NC];
-    uint32_t n, at;
-};
-__global__ void k_sd_fold(const uint32_t *part, uint64_t n, unsigned long long *misc, Totals t) {
-    bool bad = false;
-    for (uint64_t i = threadIdx.x; i < n; i += blockDim.x) bad |= part[i] != 0;
-    const int any = __syncthreads_or(bad ? 1 : 0);
-    if (threadIdx.x == 0 && any) misc[0] = 1;
-    if (threadIdx.x < t.n) misc[t.at + threadIdx.x] = *t.p[threadIdx.x];
 }
 
 __global__ void k_sd_index(SdDev d) {
@@ -481,35 +464,12 @@ __global__ void k_sd_fill(SdDev d) {
     }
 }
 
-size_t al(size_t b) { return ((b + 255) / 256) * 256; }
-
-struct Carver {
-    uint8_t *q = nullptr;
-    template <class T> T *take(size_t count) {
-        uint8_t *r = q;
-        q += al(count * sizeof(T));
-        return reinterpret_cast<T *>(r);
-    }
-};
-
-dim3 grid_for(uint64_t n) { return dim3((uint32_t)((n + 255) / 256)); }
 dim3 waves_for(uint64_t n) { return dim3((uint32_t)((n + 3) / 4)); }
 
 }  // namespace
 }  // namespace corro
 
 using namespace corro;
-
-#define SD_LAUNCH(kernel, grid, ...)                                        \
-    do {                                                                    \
-        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, __VA_ARGS__);     \
-        CORRO_HIP_TRY(hipGetLastError());                                   \
-    } while (0)
-#define SD_TRY(x)                        \
-    do {                                 \
-        int rc_ = (x);                   \
-        if (rc_ != CORRO_OK) return rc_; \
-    } while (0)
 
 extern "C" int corro_decode_states(corro_ctx *ctx, const corro_statedec_in *in, int mem, corro_statedec_out *out, int pass) {
     if (!ctx || !in || !out) return fail(CORRO_E_INVALID, "NULL argument");
@@ -555,106 +515,87 @@ extern "C" int corro_decode_states(corro_ctx *ctx, const corro_statedec_in *in, 
     d.len = in->len;
     d.F = F;
     d.P = P;
-    SD_TRY(wire_site_hash(ctx, &d.sites));
+    CORRO_TRY(wire_site_hash(ctx, &d.sites));
 
     size_t temp = 0;
-    SD_TRY(prim_inclusive_sum_u64(nullptr, &temp, nullptr, nullptr, std::max<uint64_t>(std::max(F, P), 1), s));
+    CORRO_TRY(prim_inclusive_sum_u64(nullptr, &temp, nullptr, nullptr, std::max<uint64_t>(std::max(F, P), 1), s));
     temp += 256;
     const uint64_t wg_check = (std::max(F, P) + 1 + 255) / 256;
-    const size_t stage = host ? al(in->len + 16) + al((F + 1) * 8) + 2 * al(P * 4 + 4) : 0;
-    SD_TRY(ctx->d_statedec[0].ensure(256 + al(wg_check * 4) + 2 * al(F * 4 + 4) + al(F * 16 + 16) + al(F + 1) + 11 * al((F + 1) * 8) +
-                                     al(P + 1) + 2 * NC * al((P + 1) * 8) + al(temp) + stage));
-    Carver c0{ctx->d_statedec[0].as<uint8_t>()};
-    d.misc = c0.take<unsigned long long>(32);
-    d.part_check = c0.take<uint32_t>(wg_check);
-    d.status = c0.take<int32_t>(F + 1);
-    d.f_nh = c0.take<uint32_t>(F + 1);
-    d.f_actor = c0.take<uint8_t>(F * 16 + 16);
-    d.f_has_ts = c0.take<uint8_t>(F + 1);
-    uint64_t **per_frame[11] = {&d.f_ts, &d.f_pneed, &d.f_ppart, &d.c_na, &d.c_pa, &d.c_pv, &d.c_slot,
-                                &d.o_na, &d.o_pa, &d.o_pv, &d.o_slot};
-    for (uint64_t **q : per_frame) *q = c0.take<uint64_t>(F + 1);
-    d.pair_status = c0.take<uint8_t>(P + 1);
-    for (int k = 0; k < NC; k++) d.c[k] = c0.take<uint64_t>(P + 1);
-    for (int k = 0; k < NC; k++) d.o[k] = c0.take<uint64_t>(P + 1);
-    void *tmp = c0.take<uint8_t>(temp);
-    if (host) {
-        bool ok = true;
-        auto up = [&](const void *src, size_t b, size_t room) -> const void * {
-            uint8_t *dst = c0.take<uint8_t>(room);
-            if (b && hipMemcpyAsync(dst, src, b, hipMemcpyHostToDevice, s) != hipSuccess) ok = false;
-            return dst;
-        };
-        d.buf = (const uint8_t *)up(in->buf, in->len, in->len + 16);
-        d.frame_off = (const uint64_t *)up(in->frame_off, (F + 1) * 8, (F + 1) * 8);
-        d.pair_ours = (const uint32_t *)up(in->pair_ours, P * 4, P * 4 + 4);
-        d.pair_theirs = (const uint32_t *)up(in->pair_theirs, P * 4, P * 4 + 4);
-        if (!ok) return fail(CORRO_E_DEVICE, "upload of the state frames failed");
-    } else {
-        d.buf = in->buf;
-        d.frame_off = in->frame_off;
-        d.pair_ours = in->pair_ours;
-        d.pair_theirs = in->pair_theirs;
-    }
+    Stager st{s, host};
+    void *tmp = nullptr;
+    CORRO_TRY(carve(ctx->d_statedec[0], [&](Carver &c) {
+        d.misc = c.take<unsigned long long>(32);
+        d.part_check = c.take<uint32_t>(wg_check);
+        d.status = c.take<int32_t>(F + 1);
+        d.f_nh = c.take<uint32_t>(F + 1);
+        d.f_actor = c.take<uint8_t>(F * 16 + 16);
+        d.f_has_ts = c.take<uint8_t>(F + 1);
+        uint64_t **per_frame[11] = {&d.f_ts, &d.f_pneed, &d.f_ppart, &d.c_na, &d.c_pa, &d.c_pv, &d.c_slot,
+                                    &d.o_na, &d.o_pa, &d.o_pv, &d.o_slot};
+        for (uint64_t **q : per_frame) *q = c.take<uint64_t>(F + 1);
+        d.pair_status = c.take<uint8_t>(P + 1);
+        for (int k = 0; k < NC; k++) d.c[k] = c.take<uint64_t>(P + 1);
+        for (int k = 0; k < NC; k++) d.o[k] = c.take<uint64_t>(P + 1);
+        tmp = c.take<uint8_t>(temp);
+        d.buf = c.up(in->buf, in->len, in->len + 16);
+        d.frame_off = c.up(in->frame_off, (F + 1) * 8, (F + 1) * 8);
+        d.pair_ours = c.up(in->pair_ours, P * 4, P * 4 + 4);
+        d.pair_theirs = c.up(in->pair_theirs, P * 4, P * 4 + 4);
+    }, &st));
+    if (!st.ok) return fail(CORRO_E_DEVICE, "upload of the state frames failed");
     CORRO_HIP_TRY(hipMemsetAsync(d.misc, 0, 256, s));
     for (uint64_t *o : {d.o_na, d.o_pa, d.o_pv, d.o_slot}) CORRO_HIP_TRY(hipMemsetAsync(o, 0, 8, s));
     for (int k = 0; k < NC; k++) CORRO_HIP_TRY(hipMemsetAsync(d.o[k], 0, 8, s));
-    SD_LAUNCH(k_sd_check, grid_for(std::max(F, P) + 1), d);
+    CORRO_LAUNCH(k_sd_check, grid_for(std::max(F, P) + 1), d);
     if (F) {
-        SD_LAUNCH(k_sd_count, waves_for(F), d);
+        CORRO_LAUNCH(k_sd_count, waves_for(F), d);
         const uint64_t *cs[4] = {d.c_na, d.c_pa, d.c_pv, d.c_slot};
         uint64_t *os[4] = {d.o_na, d.o_pa, d.o_pv, d.o_slot};
         for (int k = 0; k < 4; k++) {
             size_t t = temp;
-            SD_TRY(prim_inclusive_sum_u64(tmp, &t, cs[k], os[k] + 1, F, s));
+            CORRO_TRY(prim_inclusive_sum_u64(tmp, &t, cs[k], os[k] + 1, F, s));
         }
     }
-    {
-        Totals t{};
-        t.n = 4;
-        t.at = 1;
-        t.p[0] = d.o_na + F, t.p[1] = d.o_pa + F, t.p[2] = d.o_pv + F, t.p[3] = d.o_slot + F;
-        SD_LAUNCH(k_sd_fold, dim3(1), d.part_check, wg_check, d.misc, t);
-    }
+    CORRO_LAUNCH(k_flag_fold, dim3(1), d.part_check, wg_check, d.misc,
+                 fold_totals(1, {d.o_na + F, d.o_pa + F, d.o_pv + F, d.o_slot + F}));
     unsigned long long misc[5 + NC] = {};
     CORRO_HIP_TRY(hipMemcpyAsync(misc, d.misc, 5 * sizeof(misc[0]), hipMemcpyDeviceToHost, s));
     CORRO_HIP_TRY(hipStreamSynchronize(s));
     if (misc[0]) return fail(CORRO_E_INVALID, bad_input);
     const uint64_t NA = misc[1], PA = misc[2], PV = misc[3], SL = misc[4];
-    SD_TRY(ctx->d_statedec[1].ensure(al(NA * 8 + 8) + al(NA * 4 + 4) + 3 * al(PA * 8 + 8) + al(PA * 4 + 4) + 4 * al(PV * 8 + 8) +
-                                     2 * al(PV * 4 + 4) + al(SL * 4 + 4)));
-    Carver c1{ctx->d_statedec[1].as<uint8_t>()};
-    d.na_pos = c1.take<uint64_t>(NA + 1);
-    d.na_m = c1.take<uint32_t>(NA + 1);
-    d.pa_pos = c1.take<uint64_t>(PA + 1);
-    d.pa_v0 = c1.take<uint64_t>(PA + 1);
-    d.pa_seqs = c1.take<uint64_t>(PA + 1);
-    d.pa_m = c1.take<uint32_t>(PA + 1);
-    d.pv_pos = c1.take<uint64_t>(PV + 1);
-    d.pv_ver = c1.take<uint64_t>(PV + 1);
-    d.pv_sb = c1.take<uint64_t>(PV + 1);
-    d.pv_actor = c1.take<uint64_t>(PV + 1);
-    d.pv_k = c1.take<uint32_t>(PV + 1);
-    d.pv_rank = c1.take<uint32_t>(PV + 1);
-    d.slots = c1.take<uint32_t>(SL + 1);
+    CORRO_TRY(carve(ctx->d_statedec[1], [&](Carver &c) {
+        d.na_pos = c.take<uint64_t>(NA + 1);
+        d.na_m = c.take<uint32_t>(NA + 1);
+        d.pa_pos = c.take<uint64_t>(PA + 1);
+        d.pa_v0 = c.take<uint64_t>(PA + 1);
+        d.pa_seqs = c.take<uint64_t>(PA + 1);
+        d.pa_m = c.take<uint32_t>(PA + 1);
+        d.pv_pos = c.take<uint64_t>(PV + 1);
+        d.pv_ver = c.take<uint64_t>(PV + 1);
+        d.pv_sb = c.take<uint64_t>(PV + 1);
+        d.pv_actor = c.take<uint64_t>(PV + 1);
+        d.pv_k = c.take<uint32_t>(PV + 1);
+        d.pv_rank = c.take<uint32_t>(PV + 1);
+        d.slots = c.take<uint32_t>(SL + 1);
+    }));
     CORRO_HIP_TRY(hipMemsetAsync(d.slots, 0, (SL + 1) * 4, s));
     if (F) {
-        SD_LAUNCH(k_sd_index, waves_for(F), d);
-        SD_LAUNCH(k_sd_build, waves_for(F), d);
+        CORRO_LAUNCH(k_sd_index, waves_for(F), d);
+        CORRO_LAUNCH(k_sd_build, waves_for(F), d);
     }
     if (P) {
-        SD_LAUNCH(k_sd_pcount, waves_for(P), d);
+        CORRO_LAUNCH(k_sd_pcount, waves_for(P), d);
         for (int k = 0; k < NC; k++) {
             size_t t = temp;
-            SD_TRY(prim_inclusive_sum_u64(tmp, &t, d.c[k], d.o[k] + 1, P, s));
+            CORRO_TRY(prim_inclusive_sum_u64(tmp, &t, d.c[k], d.o[k] + 1, P, s));
         }
     }
     {
-        Totals t{};
+        FoldTotals t{};                            // (no partial words: the flag is folded once)
         t.n = NC;
         t.at = 5;
         for (int k = 0; k < NC; k++) t.p[k] = d.o[k] + P;
-        SD_LAUNCH(k_sd_fold, dim3(1), d.part_check, 0, d.misc, t);
+        CORRO_LAUNCH(k_flag_fold, dim3(1), d.part_check, 0, d.misc, t);
     }
     CORRO_HIP_TRY(hipMemcpyAsync(misc + 5, d.misc + 5, NC * sizeof(misc[0]), hipMemcpyDeviceToHost, s));
     CORRO_HIP_TRY(hipStreamSynchronize(s));
@@ -685,63 +626,54 @@ extern "C" int corro_decode_states(corro_ctx *ctx, const corro_statedec_in *in, 
         return fail(CORRO_E_INVALID, "sizes differ from pass 0");
     out->nunregistered = tot[7];                   // (not a size: sites may have been registered since pass 0)
     corro_statedec_out o = *out;
-    if (host) {
-        SD_TRY(ctx->d_statedec[2].ensure(8 * al((N + 1) * 8) + al(N * 16 + 16) + 2 * al((sz[0] + 1) * 8) + 2 * al((sz[1] + 1) * 8) +
-                                         2 * al((sz[2] + 1) * 8) + 2 * al((sz[3] + 1) * 8) + 2 * al((sz[4] + 1) * 8) +
-                                         2 * al((sz[5] + 1) * 8)));
-        Carver c2{ctx->d_statedec[2].as<uint8_t>()};
-        o.their_head = c2.take<uint64_t>(N + 1);
-        o.our_head = c2.take<int64_t>(N + 1);
-        o.tn_off = c2.take<uint64_t>(N + 1);
-        o.tp_off = c2.take<uint64_t>(N + 1);
-        o.on_off = c2.take<uint64_t>(N + 1);
-        o.op_off = c2.take<uint64_t>(N + 1);
-        o.entry_pair = c2.take<uint32_t>(N + 1);
-        o.entry_site = c2.take<uint32_t>(N + 1);
-        o.entry_actor = c2.take<uint8_t>(N * 16 + 16);
-        o.tn_start = c2.take<uint64_t>(sz[0] + 1);
-        o.tn_end = c2.take<uint64_t>(sz[0] + 1);
-        o.tp_ver = c2.take<uint64_t>(sz[1] + 1);
-        o.tps_off = c2.take<uint64_t>(sz[1] + 1);
-        o.tps_start = c2.take<uint64_t>(sz[2] + 1);
-        o.tps_end = c2.take<uint64_t>(sz[2] + 1);
-        o.on_start = c2.take<uint64_t>(sz[3] + 1);
-        o.on_end = c2.take<uint64_t>(sz[3] + 1);
-        o.op_ver = c2.take<uint64_t>(sz[4] + 1);
-        o.ops_off = c2.take<uint64_t>(sz[4] + 1);
-        o.ops_start = c2.take<uint64_t>(sz[5] + 1);
-        o.ops_end = c2.take<uint64_t>(sz[5] + 1);
-    }
+    if (host)
+        CORRO_TRY(carve(ctx->d_statedec[2], [&](Carver &c) {
+            o.their_head = c.take<uint64_t>(N + 1);
+            o.our_head = c.take<int64_t>(N + 1);
+            o.tn_off = c.take<uint64_t>(N + 1);
+            o.tp_off = c.take<uint64_t>(N + 1);
+            o.on_off = c.take<uint64_t>(N + 1);
+            o.op_off = c.take<uint64_t>(N + 1);
+            o.entry_pair = c.take<uint32_t>(N + 1);
+            o.entry_site = c.take<uint32_t>(N + 1);
+            o.entry_actor = c.take<uint8_t>(N * 16 + 16);
+            o.tn_start = c.take<uint64_t>(sz[0] + 1);
+            o.tn_end = c.take<uint64_t>(sz[0] + 1);
+            o.tp_ver = c.take<uint64_t>(sz[1] + 1);
+            o.tps_off = c.take<uint64_t>(sz[1] + 1);
+            o.tps_start = c.take<uint64_t>(sz[2] + 1);
+            o.tps_end = c.take<uint64_t>(sz[2] + 1);
+            o.on_start = c.take<uint64_t>(sz[3] + 1);
+            o.on_end = c.take<uint64_t>(sz[3] + 1);
+            o.op_ver = c.take<uint64_t>(sz[4] + 1);
+            o.ops_off = c.take<uint64_t>(sz[4] + 1);
+            o.ops_start = c.take<uint64_t>(sz[5] + 1);
+            o.ops_end = c.take<uint64_t>(sz[5] + 1);
+        }));
     d.out = o;
-    SD_LAUNCH(k_sd_fill, waves_for(std::max<uint64_t>(P, 1)), d);
-    if (host) {
-        bool ok = true;
-        auto down = [&](void *dst, const void *src, size_t b) {
-            if (b && hipMemcpyAsync(dst, src, b, hipMemcpyDeviceToHost, s) != hipSuccess) ok = false;
-        };
-        down(out->their_head, o.their_head, N * 8);
-        down(out->our_head, o.our_head, N * 8);
-        down(out->tn_off, o.tn_off, (N + 1) * 8);
-        down(out->tp_off, o.tp_off, (N + 1) * 8);
-        down(out->on_off, o.on_off, (N + 1) * 8);
-        down(out->op_off, o.op_off, (N + 1) * 8);
-        down(out->entry_pair, o.entry_pair, N * 4);
-        down(out->entry_site, o.entry_site, N * 4);
-        down(out->entry_actor, o.entry_actor, N * 16);
-        down(out->tn_start, o.tn_start, sz[0] * 8);
-        down(out->tn_end, o.tn_end, sz[0] * 8);
-        down(out->tp_ver, o.tp_ver, sz[1] * 8);
-        down(out->tps_off, o.tps_off, (sz[1] + 1) * 8);
-        down(out->tps_start, o.tps_start, sz[2] * 8);
-        down(out->tps_end, o.tps_end, sz[2] * 8);
-        down(out->on_start, o.on_start, sz[3] * 8);
-        down(out->on_end, o.on_end, sz[3] * 8);
-        down(out->op_ver, o.op_ver, sz[4] * 8);
-        down(out->ops_off, o.ops_off, (sz[4] + 1) * 8);
-        down(out->ops_start, o.ops_start, sz[5] * 8);
-        down(out->ops_end, o.ops_end, sz[5] * 8);
-        if (!ok) return fail(CORRO_E_DEVICE, "download of the decoded states failed");
-    }
+    CORRO_LAUNCH(k_sd_fill, waves_for(std::max<uint64_t>(P, 1)), d);
+    st.down(out->their_head, o.their_head, N * 8);
+    st.down(out->our_head, o.our_head, N * 8);
+    st.down(out->tn_off, o.tn_off, (N + 1) * 8);
+    st.down(out->tp_off, o.tp_off, (N + 1) * 8);
+    st.down(out->on_off, o.on_off, (N + 1) * 8);
+    st.down(out->op_off, o.op_off, (N + 1) * 8);
+    st.down(out->entry_pair, o.entry_pair, N * 4);
+    st.down(out->entry_site, o.entry_site, N * 4);
+    st.down(out->entry_actor, o.entry_actor, N * 16);
+    st.down(out->tn_start, o.tn_start, sz[0] * 8);
+    st.down(out->tn_end, o.tn_end, sz[0] * 8);
+    st.down(out->tp_ver, o.tp_ver, sz[1] * 8);
+    st.down(out->tps_off, o.tps_off, (sz[1] + 1) * 8);
+    st.down(out->tps_start, o.tps_start, sz[2] * 8);
+    st.down(out->tps_end, o.tps_end, sz[2] * 8);
+    st.down(out->on_start, o.on_start, sz[3] * 8);
+    st.down(out->on_end, o.on_end, sz[3] * 8);
+    st.down(out->op_ver, o.op_ver, sz[4] * 8);
+    st.down(out->ops_off, o.ops_off, (sz[4] + 1) * 8);
+    st.down(out->ops_start, o.ops_start, sz[5] * 8);
+    st.down(out->ops_end, o.ops_end, sz[5] * 8);
+    if (!st.ok) return fail(CORRO_E_DEVICE, "download of the decoded states failed");
     CORRO_HIP_TRY(hipStreamSynchronize(s));
     return CORRO_OK;
 }

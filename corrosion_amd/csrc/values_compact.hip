@@ -23,6 +23,7 @@
 #include <algorithm>
 
 #include "internal.h"
+#include "scratch_core.h"
 #include "merge_kernels.h"
 
 namespace corro {
@@ -198,12 +199,6 @@ static __global__ void k_vc_rewrite(VcDev d, Rec *__restrict__ heap) {
         heap[d.heap[i]].v1 = ((d.off[i] - d.dead[i]) << 24) | d.len[i];
 }
 
-#define VC_TRY(x)                        \
-    do {                                 \
-        int rc_ = (x);                   \
-        if (rc_ != CORRO_OK) return rc_; \
-    } while (0)
-
 int values_compact(corro_ctx *ctx, bool dry_run, uint64_t reserve, uint64_t *live_bytes, uint64_t *arena_before,
                    uint64_t *arena_after) {
     CORRO_HIP_TRY(hipSetDevice(ctx->device));
@@ -227,7 +222,7 @@ int values_compact(corro_ctx *ctx, bool dry_run, uint64_t reserve, uint64_t *liv
     // live long records, counted (the count sizes every array)
     unsigned long long n64 = 0;
     if (before && ctx->state_total) {
-        VC_TRY(cnt_buf.b.ensure(256));
+        CORRO_TRY(cnt_buf.b.ensure(256));
         CORRO_HIP_TRY(hipMemsetAsync(cnt_buf.b.p, 0, 16, s));
         hipLaunchKernelGGL(k_vc_collect, grid_for(nent), blk, 0, s, rs, nent, cnt_buf.b.as<unsigned long long>(), 0ULL,
                            (uint64_t *)nullptr, (uint32_t *)nullptr);
@@ -250,15 +245,14 @@ int values_compact(corro_ctx *ctx, bool dry_run, uint64_t reserve, uint64_t *liv
     size_t temp = 0;
     {
         size_t t0 = 0, t1 = 0, t2 = 0, t3 = 0;
-        VC_TRY(ovf_sort_pairs(nullptr, &t0, nullptr, nullptr, nullptr, nullptr, n, key_bits, s));
-        VC_TRY(prim_inclusive_max_u64(nullptr, &t1, nullptr, nullptr, n, s));
-        VC_TRY(prim_inclusive_sum_u64(nullptr, &t2, nullptr, nullptr, n, s));
-        VC_TRY(prim_inclusive_scan_u32_u64(nullptr, &t3, nullptr, nullptr, n, s));
+        CORRO_TRY(ovf_sort_pairs(nullptr, &t0, nullptr, nullptr, nullptr, nullptr, n, key_bits, s));
+        CORRO_TRY(prim_inclusive_max_u64(nullptr, &t1, nullptr, nullptr, n, s));
+        CORRO_TRY(prim_inclusive_sum_u64(nullptr, &t2, nullptr, nullptr, n, s));
+        CORRO_TRY(prim_inclusive_scan_u32_u64(nullptr, &t3, nullptr, nullptr, n, s));
         temp = std::max(std::max(t0, t1), std::max(t2, t3));
     }
-    auto al = [](uint64_t x) { return (x + 255) & ~255ULL; };
-    const uint64_t c8 = al((uint64_t)n * 8), c4 = al((uint64_t)n * 4);
-    VC_TRY(scratch.b.ensure(6 * c8 + 3 * c4 + 256 + temp + 256));
+    const uint64_t c8 = al256((uint64_t)n * 8), c4 = al256((uint64_t)n * 4);
+    CORRO_TRY(scratch.b.ensure(6 * c8 + 3 * c4 + 256 + temp + 256));
     uint8_t *p = scratch.b.as<uint8_t>();
     auto take = [&](uint64_t bytes) {
         uint8_t *r = p;
@@ -285,15 +279,15 @@ int values_compact(corro_ctx *ctx, bool dry_run, uint64_t reserve, uint64_t *liv
     CORRO_HIP_TRY(hipMemsetAsync(d_count, 0, 16, s));
     hipLaunchKernelGGL(k_vc_collect, grid_for(nent), blk, 0, s, rs, nent, d_count, (uint64_t)n, key_in, heap_in);
     CORRO_HIP_TRY(hipGetLastError());
-    VC_TRY(ovf_sort_pairs(d_temp, &temp, key_in, d.off, heap_in, d.heap, n, key_bits, s));
+    CORRO_TRY(ovf_sort_pairs(d_temp, &temp, key_in, d.off, heap_in, d.heap, n, key_bits, s));
     const dim3 grid = grid_for(n);
     hipLaunchKernelGGL(k_vc_spans, grid, blk, 0, s, d, rs.heap, before, d_bad);
     CORRO_HIP_TRY(hipGetLastError());
-    VC_TRY(prim_inclusive_max_u64(d_temp, &temp, d.end, d.emax, n, s));
+    CORRO_TRY(prim_inclusive_max_u64(d_temp, &temp, d.end, d.emax, n, s));
     hipLaunchKernelGGL(k_vc_pieces, grid, blk, 0, s, d);
     CORRO_HIP_TRY(hipGetLastError());
-    VC_TRY(prim_inclusive_sum_u64(d_temp, &temp, d.gap, d.dead, n, s));
-    VC_TRY(prim_inclusive_scan_u32_u64(d_temp, &temp, d.cnt, d.cinc, n, s));
+    CORRO_TRY(prim_inclusive_sum_u64(d_temp, &temp, d.gap, d.dead, n, s));
+    CORRO_TRY(prim_inclusive_scan_u32_u64(d_temp, &temp, d.cnt, d.cinc, n, s));
     unsigned long long h_cnt[2] = {}, h_end = 0, h_dead = 0, h_chunks = 0;
     CORRO_HIP_TRY(hipMemcpyAsync(h_cnt, d_count, 16, hipMemcpyDeviceToHost, s));
     CORRO_HIP_TRY(hipMemcpyAsync(&h_end, d.emax + (n - 1), 8, hipMemcpyDeviceToHost, s));
@@ -306,7 +300,7 @@ int values_compact(corro_ctx *ctx, bool dry_run, uint64_t reserve, uint64_t *liv
     if (live > before || h_dead > h_end) return fail(CORRO_E_DEVICE, "internal: live value bytes exceed the arena");
     if (dry_run) return report(live, before);
 
-    VC_TRY(fresh.b.ensure(top + reserve));
+    CORRO_TRY(fresh.b.ensure(top + reserve));
     const uint8_t *const src = ctx->d_arena.as<uint8_t>();
     const uint64_t waves = (h_chunks + VC_GROUP - 1) / VC_GROUP;
     hipLaunchKernelGGL(k_vc_copy, dim3((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((waves + 3) / 4, 4096))), blk, 0, s,

@@ -37,6 +37,7 @@
 #include <vector>
 
 #include "internal.h"
+#include "scratch_core.h"
 
 namespace corro {
 namespace {
@@ -531,7 +532,6 @@ __global__ void __launch_bounds__(64) k_wire_decode(WireDev d) {
     else body(g, false);
 }
 
-size_t al(size_t b) { return ((b + 255) / 256) * 256; }
 
 uint64_t hmix(uint64_t x) {
     x ^= x >> 33; x *= 0xff51afd7ed558ccdULL;
@@ -577,13 +577,13 @@ int wire_tables(corro_ctx *ctx) {
             }
         }
         const size_t nt = toff.size(), nc = coff.size();
-        const size_t bytes = al(names.size() + 1) + 4 * al(nt * 4 + 4) + 2 * al(nc * 4 + 4);
+        const size_t bytes = al256(names.size() + 1) + 4 * al256(nt * 4 + 4) + 2 * al256(nc * 4 + 4);
         if (int rc = ctx->d_wire_schema.ensure(bytes)) return rc;
         uint8_t *q = ctx->d_wire_schema.as<uint8_t>();
         auto put = [&](const void *src, size_t b) -> uint8_t * {
             uint8_t *r = q;
             if (b && hipMemcpy(r, src, b, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-            q += al(b + 4);
+            q += al256(b + 4);
             return r;
         };
         ctx->wire_names = put(names.data(), names.size());
@@ -612,11 +612,11 @@ int wire_tables(corro_ctx *ctx) {
             hi[h] = b;
             ord[h] = (uint32_t)i;
         }
-        if (int rc = ctx->d_wire_sites.ensure(al(H * 8ULL) * 2 + al(H * 4ULL))) return rc;
+        if (int rc = ctx->d_wire_sites.ensure(al256(H * 8ULL) * 2 + al256(H * 4ULL))) return rc;
         uint8_t *q = ctx->d_wire_sites.as<uint8_t>();
         CORRO_HIP_TRY(hipMemcpy(q, lo.data(), H * 8ULL, hipMemcpyHostToDevice));
-        CORRO_HIP_TRY(hipMemcpy(q + al(H * 8ULL), hi.data(), H * 8ULL, hipMemcpyHostToDevice));
-        CORRO_HIP_TRY(hipMemcpy(q + 2 * al(H * 8ULL), ord.data(), H * 4ULL, hipMemcpyHostToDevice));
+        CORRO_HIP_TRY(hipMemcpy(q + al256(H * 8ULL), hi.data(), H * 8ULL, hipMemcpyHostToDevice));
+        CORRO_HIP_TRY(hipMemcpy(q + 2 * al256(H * 8ULL), ord.data(), H * 4ULL, hipMemcpyHostToDevice));
         ctx->wire_hmask = H - 1;
         ctx->wire_sites_n = n;
     }
@@ -633,8 +633,8 @@ int wire_site_hash(corro_ctx *ctx, SiteHash *out) {
     const uint8_t *sq = ctx->d_wire_sites.as<uint8_t>();
     const uint32_t H = ctx->wire_hmask + 1;
     out->lo = (const uint64_t *)sq;
-    out->hi = (const uint64_t *)(sq + al(H * 8ULL));
-    out->ord = (const uint32_t *)(sq + 2 * al(H * 8ULL));
+    out->hi = (const uint64_t *)(sq + al256(H * 8ULL));
+    out->ord = (const uint32_t *)(sq + 2 * al256(H * 8ULL));
     out->mask = ctx->wire_hmask;
     return CORRO_OK;
 }
@@ -677,16 +677,16 @@ extern "C" int corro_decode_frames(corro_ctx *ctx, const uint8_t *buf, uint64_t 
     const uint64_t NC = pass == 1 ? out->nchanges : 0, NS = pass == 1 ? out->nsets : 0;
     const uint32_t ucap = 4096;
     // scratch: bytes, frame index, headers, offsets, unknown sites, outputs staged for host mode
-    const size_t hdr = 6 * al(F * 4ULL) + 6 * al(F * 8ULL) + al(F * 16ULL);
-    const size_t outb = (mem == CORRO_MEM_HOST && pass == 1) ? (al(NC * 8) * 6 + al(NC * 4) * 4 + al(NC) * 2) : 0;
-    const size_t need = al(len) + al(F * 8ULL) + al(F * 4ULL) + hdr + 2 * al((F + 1) * 8ULL) + al(NC * 4 + 4) +
-                        al(ucap * 16ULL) + 256 + outb + 2 * al(NS * 8 + 8) + al(NC * 8 + 8) + al(NC * 12 + 12) +
-                        al(ctx->tables.size() + 1);
+    const size_t hdr = 6 * al256(F * 4ULL) + 6 * al256(F * 8ULL) + al256(F * 16ULL);
+    const size_t outb = (mem == CORRO_MEM_HOST && pass == 1) ? (al256(NC * 8) * 6 + al256(NC * 4) * 4 + al256(NC) * 2) : 0;
+    const size_t need = al256(len) + al256(F * 8ULL) + al256(F * 4ULL) + hdr + 2 * al256((F + 1) * 8ULL) + al256(NC * 4 + 4) +
+                        al256(ucap * 16ULL) + 256 + outb + 2 * al256(NS * 8 + 8) + al256(NC * 8 + 8) + al256(NC * 12 + 12) +
+                        al256(ctx->tables.size() + 1);
     if (int rc = ctx->d_wire.ensure(need)) return rc;
     uint8_t *q = ctx->d_wire.as<uint8_t>();
     auto carve = [&](size_t b) {
         uint8_t *r = q;
-        q += al(b);
+        q += al256(b);
         return r;
     };
     WireDev d{};
@@ -785,8 +785,8 @@ extern "C" int corro_decode_frames(corro_ctx *ctx, const uint8_t *buf, uint64_t 
         uint8_t *sq = ctx->d_wire_sites.as<uint8_t>();
         const uint32_t H = ctx->wire_hmask + 1;
         d.hlo = (const uint64_t *)sq;
-        d.hhi = (const uint64_t *)(sq + al(H * 8ULL));
-        d.hord = (const uint32_t *)(sq + 2 * al(H * 8ULL));
+        d.hhi = (const uint64_t *)(sq + al256(H * 8ULL));
+        d.hord = (const uint32_t *)(sq + 2 * al256(H * 8ULL));
         d.hmask = ctx->wire_hmask;
         CORRO_HIP_TRY(hipMemsetAsync(d.nunknown, 0, 24, s));
         if (NC) CORRO_HIP_TRY(hipMemsetAsync(d.pkref, 0, NC * 8, s));

@@ -28,10 +28,9 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstring>
-#include <vector>
 
 #include "internal.h"
+#include "scratch.h"
 
 namespace corro {
 int prim_inclusive_scan_u32_u64(void *temp, size_t *temp_bytes, const uint32_t *in, uint64_t *out, uint64_t n,
@@ -424,8 +423,6 @@ __global__ void __launch_bounds__(64) k_enc_write(EncDev d) {
     }
 }
 
-size_t al(size_t b) { return ((b + 255) / 256) * 256; }
-
 }  // namespace
 }  // namespace corro
 
@@ -477,17 +474,6 @@ extern "C" int corro_encode_changesets(corro_ctx *ctx, const corro_encode_in *in
         if (int rc = prim_inclusive_sum_u64(nullptr, &t, nullptr, nullptr, S, s)) return rc;
         temp = std::max(temp, t);
     }
-    const size_t in_stage = host ? al(S * 4) + 7 * al(S * 8) + 6 * al(R * 8) + 3 * al(R * 4) + 2 * al(R) : 0;
-    const size_t out_stage = host && pass == 1 ? al(NB) + al((F + 1) * 8) + 3 * al(F * 8) + al(F * 4) : 0;
-    const size_t need = al(nsites * 16 + 16) + 2 * al(R * 4) + 2 * al((R + 1) * 8) + 2 * al(S * 8) + 2 * al((S + 1) * 8) +
-                        256 + al(temp + 256) + al(F * 4) + in_stage + out_stage;
-    if (int rc = ctx->d_wire_enc.ensure(need)) return rc;
-    uint8_t *q = ctx->d_wire_enc.as<uint8_t>();
-    auto carve = [&](size_t b) {
-        uint8_t *r = q;
-        q += al(b);
-        return r;
-    };
     EncDev d{};
     d.n = S;
     d.nrows = R;
@@ -506,65 +492,59 @@ extern "C" int corro_encode_changesets(corro_ctx *ctx, const corro_encode_in *in
     d.pkdir = ctx->d_pkdir.as<PkDir>();
     d.arena = ctx->d_arena.as<uint8_t>();
     d.arena_top = ctx->arena_top;
-    {
-        uint8_t *ds = carve(nsites * 16 + 16);
-        std::vector<uint8_t> hs(nsites * 16 + 16, 0);
-        for (size_t i = 0; i < nsites; i++) std::memcpy(hs.data() + 16 * i, ctx->sites[i].data(), 16);
-        CORRO_HIP_TRY(hipMemcpy(ds, hs.data(), nsites * 16, hipMemcpyHostToDevice));
-        d.sites = ds;
-    }
-    d.est = (uint32_t *)carve(R * 4);
-    d.enc = (uint32_t *)carve(R * 4);
-    d.pest = (uint64_t *)carve((R + 1) * 8);
-    d.penc = (uint64_t *)carve((R + 1) * 8);
-    d.span_nfr = (uint64_t *)carve(S * 8);
-    d.span_bytes = (uint64_t *)carve(S * 8);
-    d.span_foff = (uint64_t *)carve((S + 1) * 8);
-    d.span_boff = (uint64_t *)carve((S + 1) * 8);
-    d.err = (uint32_t *)carve(256);
-    void *dtemp = carve(temp + 256);
-    d.fspan = (uint32_t *)carve(F * 4);
-    // inputs: the caller's device arrays, or staged copies of its host arrays
-    if (host) {
-        auto up = [&](const void *src, size_t b) -> const void * {
-            uint8_t *dst = carve(b);
-            if (b && hipMemcpyAsync(dst, src, b, hipMemcpyHostToDevice, s) != hipSuccess) return nullptr;
-            return dst;
-        };
-        d.site = (const uint32_t *)up(in->site, S * 4);
-        d.version = (const int64_t *)up(in->version, S * 8);
-        d.last_seq = (const uint64_t *)up(in->last_seq, S * 8);
-        d.ts = (const uint64_t *)up(in->ts, S * 8);
-        d.seq_start = (const uint64_t *)up(in->seq_start, S * 8);
-        d.seq_end = (const uint64_t *)up(in->seq_end, S * 8);
-        d.row_off = (const uint64_t *)up(in->row_off, S * 8);
-        d.row_count = (const uint64_t *)up(in->row_count, S * 8);
-        d.rows.pk = (uint64_t *)up(hr.pk, R * 8);
-        d.rows.col_version = (int64_t *)up(hr.col_version, R * 8);
-        d.rows.db_version = (int64_t *)up(hr.db_version, R * 8);
-        d.rows.cl = (int64_t *)up(hr.cl, R * 8);
-        d.rows.val0 = (uint64_t *)up(hr.val0, R * 8);
-        d.rows.val1 = (uint64_t *)up(hr.val1, R * 8);
-        d.rows.table_cid = (uint32_t *)up(hr.table_cid, R * 4);
-        d.rows.seq = (uint32_t *)up(hr.seq, R * 4);
-        d.rows.site = (uint32_t *)up(hr.site, R * 4);
-        d.rows.val_type = (uint8_t *)up(hr.val_type, R);
-        d.rows.val_len = (uint8_t *)up(hr.val_len, R);
-        if (!d.site || !d.version || !d.last_seq || !d.ts || !d.seq_start || !d.seq_end || !d.row_off || !d.row_count ||
-            !d.rows.pk || !d.rows.col_version || !d.rows.db_version || !d.rows.cl || !d.rows.val0 || !d.rows.val1 ||
-            !d.rows.table_cid || !d.rows.seq || !d.rows.site || !d.rows.val_type || !d.rows.val_len)
-            return fail(CORRO_E_DEVICE, "upload of the spans or rows failed");
-    } else {
-        d.site = in->site;
-        d.version = in->version;
-        d.last_seq = in->last_seq;
-        d.ts = in->ts;
-        d.seq_start = in->seq_start;
-        d.seq_end = in->seq_end;
-        d.row_off = in->row_off;
-        d.row_count = in->row_count;
-        d.rows = hr;
-    }
+    // the caller's device arrays, or staged copies of its host arrays; outputs likewise (pass 1)
+    d.buf = out->buf;
+    d.frame_off = out->frame_off;
+    d.fss = out->frame_seq_start;
+    d.fse = out->frame_seq_end;
+    d.fro = out->frame_row_off;
+    d.frows = out->frame_rows;
+    Stager st{s, host};
+    void *dtemp = nullptr;
+    uint8_t *dsites = nullptr;
+    CORRO_TRY(carve(ctx->d_wire_enc, [&](Carver &c) {
+        d.sites = dsites = c.take<uint8_t>(nsites * 16 + 16);
+        d.est = c.take<uint32_t>(R);
+        d.enc = c.take<uint32_t>(R);
+        d.pest = c.take<uint64_t>(R + 1);
+        d.penc = c.take<uint64_t>(R + 1);
+        d.span_nfr = c.take<uint64_t>(S);
+        d.span_bytes = c.take<uint64_t>(S);
+        d.span_foff = c.take<uint64_t>(S + 1);
+        d.span_boff = c.take<uint64_t>(S + 1);
+        d.err = c.take<uint32_t>(64);
+        dtemp = c.take<uint8_t>(temp + 256);
+        d.fspan = c.take<uint32_t>(F);
+        d.site = c.up(in->site, S * 4, S * 4);
+        d.version = c.up(in->version, S * 8, S * 8);
+        d.last_seq = c.up(in->last_seq, S * 8, S * 8);
+        d.ts = c.up(in->ts, S * 8, S * 8);
+        d.seq_start = c.up(in->seq_start, S * 8, S * 8);
+        d.seq_end = c.up(in->seq_end, S * 8, S * 8);
+        d.row_off = c.up(in->row_off, S * 8, S * 8);
+        d.row_count = c.up(in->row_count, S * 8, S * 8);
+        d.rows.pk = c.up(hr.pk, R * 8, R * 8);
+        d.rows.col_version = c.up(hr.col_version, R * 8, R * 8);
+        d.rows.db_version = c.up(hr.db_version, R * 8, R * 8);
+        d.rows.cl = c.up(hr.cl, R * 8, R * 8);
+        d.rows.val0 = c.up(hr.val0, R * 8, R * 8);
+        d.rows.val1 = c.up(hr.val1, R * 8, R * 8);
+        d.rows.table_cid = c.up(hr.table_cid, R * 4, R * 4);
+        d.rows.seq = c.up(hr.seq, R * 4, R * 4);
+        d.rows.site = c.up(hr.site, R * 4, R * 4);
+        d.rows.val_type = c.up(hr.val_type, R, R);
+        d.rows.val_len = c.up(hr.val_len, R, R);
+        if (host && pass == 1) {
+            d.buf = c.take<uint8_t>(NB);
+            d.frame_off = c.take<uint64_t>(F + 1);
+            d.fss = c.take<uint64_t>(F);
+            d.fse = c.take<uint64_t>(F);
+            d.fro = c.take<uint64_t>(F);
+            d.frows = c.take<uint32_t>(F);
+        }
+    }, &st));
+    if (!st.ok) return fail(CORRO_E_DEVICE, "upload of the spans or rows failed");
+    CORRO_TRY(upload_site_table(ctx, dsites, s));
     // sizes, their prefix sums, frames and bytes per span
     CORRO_HIP_TRY(hipMemsetAsync(d.err, 0, 256, s));
     CORRO_HIP_TRY(hipMemsetAsync(d.pest, 0, 8, s));
@@ -608,21 +588,6 @@ extern "C" int corro_encode_changesets(corro_ctx *ctx, const corro_encode_in *in
     if (tot[0] != F || tot[1] != NB) return fail(CORRO_E_INVALID, "sizes differ from pass 0");
     d.nframes = F;
     d.nbytes = NB;
-    if (host) {
-        d.buf = carve(NB);
-        d.frame_off = (uint64_t *)carve((F + 1) * 8);
-        d.fss = (uint64_t *)carve(F * 8);
-        d.fse = (uint64_t *)carve(F * 8);
-        d.fro = (uint64_t *)carve(F * 8);
-        d.frows = (uint32_t *)carve(F * 4);
-    } else {
-        d.buf = out->buf;
-        d.frame_off = out->frame_off;
-        d.fss = out->frame_seq_start;
-        d.fse = out->frame_seq_end;
-        d.fro = out->frame_row_off;
-        d.frows = out->frame_rows;
-    }
     hipLaunchKernelGGL(k_enc_chain, dim3((uint32_t)((S + 127) / 128)), dim3(128), 0, s, d, 1);
     CORRO_HIP_TRY(hipGetLastError());
     if (NB) {
