@@ -45,7 +45,7 @@ EXPORTS = [
     "corro_plan_requests", "corro_decode_requests", "corro_need_spans",
     "corro_need_tails", "corro_assemble_answers",
     "corro_bookie_buffered_index", "corro_buffered_spans", "corro_assemble_answers_buffered",
-    "corro_decode_states",
+    "corro_decode_states", "corro_bookie_sync_book", "corro_encode_states",
 ]
 
 CORRO_CS_FULL, CORRO_CS_EMPTY, CORRO_CS_EMPTY_SET = 0, 1, 2
@@ -263,6 +263,25 @@ class SyncState(C.Structure):
         "pseq_off", "pseq_start", "pseq_end")]
 
 
+_BOOK_ROWS = ("actor", "max", "gap_off", "gap_start", "gap_end", "part_off", "part_version", "part_last_seq",
+              "psr_off", "psr_start", "psr_end")
+
+
+class SyncBook(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("nrows", "ngaps", "nparts", "npsr")] + [(k, C.c_void_p) for k in _BOOK_ROWS]
+
+
+class StateEncIn(C.Structure):
+    _fields_ = [("nstates", C.c_uint64)] + [(k, C.c_void_p) for k in ("self_actor", "has_ts", "ts", "state_row_off")] + [
+        (k, C.c_uint64) for k in ("nrows", "ngaps", "nparts", "npsr")] + [(k, C.c_void_p) for k in _BOOK_ROWS] + [
+        ("max_payload", C.c_uint64)]
+
+
+class StateEncOut(C.Structure):
+    _fields_ = [("total_bytes", C.c_uint64)] + [(k, C.c_void_p) for k in (
+        "state_status", "frame_off", "n_heads", "n_need", "n_partial", "buf")]
+
+
 _lib = None
 
 
@@ -362,6 +381,8 @@ def lib():
         "corro_bookie_contains_all": (i32, [vp, vp, u64, u64, i32, u64, u64, vp]),
         "corro_bookie_partial": (i32, [vp, vp, u64, vp, vp, u64, vp, vp]),
         "corro_generate_sync": (i32, [vp, vp, C.POINTER(SyncState), i32]),
+        "corro_bookie_sync_book": (i32, [vp, C.POINTER(SyncBook), i32]),
+        "corro_encode_states": (i32, [vp, C.POINTER(StateEncIn), i32, C.POINTER(StateEncOut), i32]),
         "corro_partition_ranks": (i32, [vp, C.POINTER(Changes), u32, C.POINTER(Changes), vp]),
         "corro_packed_record_bytes": (i32, [C.POINTER(Changes), vp]),
         "corro_partition_packed": (i32, [vp, C.POINTER(Changes), u32, vp, vp, vp]),

@@ -139,6 +139,27 @@ class Bookie:
                                              C.byref(c), C.byref(last)))
         return [(int(s[i]), int(e[i])) for i in range(n)], int(last.value)
 
+    def sync_book(self):
+        """The bookie as one sync book (corro_bookie_sync_book): what generate_sync reads, one row per actor
+        in generate_sync's order, as numpy arrays keyed like corro_sync_book -- "actor" (nrows x 16), "max"
+        (int64, -1 = None), the needed gaps ("gap_off", "gap_start", "gap_end") and every partial
+        ("part_off", "part_version", "part_last_seq") with the seq ranges it holds ("psr_off", "psr_start",
+        "psr_end"). sync.state_frames_from_books takes it."""
+        lib = L.lib()
+        bk = L.SyncBook()
+        L.check(lib.corro_bookie_sync_book(self._h, C.byref(bk), 0))
+        nr, ng, npt, ns = bk.nrows, bk.ngaps, bk.nparts, bk.npsr
+        sizes = {"actor": 16 * nr, "max": nr, "gap_off": nr + 1, "gap_start": ng, "gap_end": ng, "part_off": nr + 1,
+                 "part_version": npt, "part_last_seq": npt, "psr_off": npt + 1, "psr_start": ns, "psr_end": ns}
+        dts = {"actor": np.uint8, "max": np.int64}
+        bufs = {k: np.zeros(max(1, n), dts.get(k, np.uint64)) for k, n in sizes.items()}
+        for k, a in bufs.items():
+            setattr(bk, k, a.ctypes.data)
+        L.check(lib.corro_bookie_sync_book(self._h, C.byref(bk), 1))
+        book = {k: bufs[k][:n] for k, n in sizes.items()}
+        book["actor"] = book["actor"].reshape(nr, 16)
+        return book
+
 
 class Agent:
     """One node's writer: the device merge engine + its Bookie (agent.rs:480-482 single writer)."""
@@ -337,6 +358,22 @@ class Agent:
         r = C.c_int()
         L.check(L.lib().corro_process_fully_buffered(self.engine._h, self.bookie._h, actor, version, C.byref(r)))
         return bool(r.value)
+
+    def sync_book(self):
+        """The bookie as one sync book (Bookie.sync_book): what generate_sync reads, one row per actor in
+        generate_sync's order. sync.state_frames_from_books takes it."""
+        return self.bookie.sync_book()
+
+    def generate_sync_frame(self, last_cleared_ts=None, device=False):
+        """This node's SyncMessageV1::State as one length-delimited frame, generated and encoded on the
+        device from the sync book (corro_encode_states): the bytes wire.frame(wire.encode_sync_state(
+        self.generate_sync())) gives. Returns bytes, or with device=True the CUDA uint8 tensor."""
+        from .sync import state_frames_from_books
+        res = state_frames_from_books(self.engine, [self.sync_book()], [self.actor_id], ts=[last_cleared_ts], device=device)
+        st = int(res["state_status"][0])
+        if st != 0:
+            raise L.CorroError(st, "the bookie's sync book does not encode (not canonical, or larger than a frame)")
+        return res["buf"] if device else res["buf"].tobytes()
 
     def generate_sync(self):
         lib = L.lib()

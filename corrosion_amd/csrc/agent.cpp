@@ -2816,4 +2816,59 @@ int corro_generate_sync(corro_bookie *bk, const uint8_t *self_actor, corro_sync_
     return CORRO_OK;
 }
 
+// What generate_sync reads, as CSR over every actor of the bookie in the walk's order (corro_sync_book):
+// max (-1 = None), the needed gaps, and every partial with its last_seq and the seq ranges it holds.
+// pass 0 fills the four counts; pass 1 checks them against the bookie before it writes anything.
+int corro_bookie_sync_book(corro_bookie *bk, corro_sync_book *o, int pass) {
+    if (!bk || !o) return fail(CORRO_E_INVALID, "NULL argument");
+    if (pass != 0 && pass != 1) return fail(CORRO_E_INVALID, "pass must be 0 or 1");
+    uint64_t nr = 0, ng = 0, np = 0, ns = 0;
+    for (const auto &[actor, booked] : bk->actors) {
+        nr++;
+        ng += booked.needed.ranges().size();
+        np += booked.partials.size();
+        for (const auto &[v, p] : booked.partials) ns += p.seqs.ranges().size();
+    }
+    if (pass == 0) {
+        o->nrows = nr;
+        o->ngaps = ng;
+        o->nparts = np;
+        o->npsr = ns;
+        return CORRO_OK;
+    }
+    if (o->nrows != nr || o->ngaps != ng || o->nparts != np || o->npsr != ns)
+        return fail(CORRO_E_INVALID, "counts differ from pass 0");
+    if (!o->gap_off || !o->part_off || !o->psr_off || (nr && (!o->actor || !o->max)) || (ng && (!o->gap_start || !o->gap_end)) ||
+        (np && (!o->part_version || !o->part_last_seq)) || (ns && (!o->psr_start || !o->psr_end)))
+        return fail(CORRO_E_INVALID, "an output array is NULL");
+    nr = ng = np = ns = 0;
+    for (const auto &[actor, booked] : bk->actors) {
+        std::memcpy(o->actor + 16 * nr, actor.data(), 16);
+        o->max[nr] = booked.has_max ? (int64_t)booked.max : -1;
+        o->gap_off[nr] = ng;
+        o->part_off[nr] = np;
+        for (const auto &r : booked.needed.ranges()) {
+            o->gap_start[ng] = r.first;
+            o->gap_end[ng] = r.second;
+            ng++;
+        }
+        for (const auto &[v, p] : booked.partials) {
+            o->part_version[np] = v;
+            o->part_last_seq[np] = p.last_seq;
+            o->psr_off[np] = ns;
+            for (const auto &r : p.seqs.ranges()) {
+                o->psr_start[ns] = r.first;
+                o->psr_end[ns] = r.second;
+                ns++;
+            }
+            np++;
+        }
+        nr++;
+    }
+    o->gap_off[nr] = ng;
+    o->part_off[nr] = np;
+    o->psr_off[np] = ns;
+    return CORRO_OK;
+}
+
 }  // extern "C"

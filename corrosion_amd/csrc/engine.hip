@@ -726,6 +726,7 @@ void corro_ctx_destroy(corro_ctx *ctx) {
     for (DevBuf &b : ctx->d_req) b.release();
     for (DevBuf &b : ctx->d_reqdec) b.release();
     for (DevBuf &b : ctx->d_statedec) b.release();
+    for (DevBuf &b : ctx->d_stateenc) b.release();
     ctx->d_pkdir.release();
     ctx->d_pk_scratch.release();
     ctx->d_pk_bad.release();

@@ -300,6 +300,9 @@ struct corro_ctx {
     // state decode (state_decode.hip): [0] staged host inputs, per-frame / per-pair counts, offsets and
     // rocPRIM temp, [1] the per-frame offset and join tables, [2] staged host outputs
     corro::DevBuf d_statedec[3];
+    // state encode (state_encode.hip): [0] staged host inputs, the per-gap / per-partial / per-row /
+    // per-state sizes, their scans and rocPRIM temp, [1] staged host outputs
+    corro::DevBuf d_stateenc[2];
     bool wire_schema_ready = false;
     const uint8_t *wire_names = nullptr;
     const uint32_t *wire_toff = nullptr, *wire_tlen = nullptr, *wire_tbase = nullptr, *wire_tn = nullptr,

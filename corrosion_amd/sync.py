@@ -544,6 +544,118 @@ def requests_from_state_frames(engine, buf, frame_off, sessions, chunk=10, drain
     return res
 
 
+_BOOK_DT = {"actor": np.uint8, "max": np.int64}
+_STATEENC_OUT = (("state_status", np.int32, 0), ("frame_off", np.uint64, 1), ("n_heads", np.uint32, 0),
+                 ("n_need", np.uint32, 0), ("n_partial", np.uint32, 0))
+
+
+def concat_books(books):
+    """Sync books (Agent.sync_book() dicts) -> one book of shared row arrays plus "state_row_off"
+    (len(books) + 1): state b's rows are [state_row_off[b], state_row_off[b + 1])."""
+    out = {k: [] for k in L._BOOK_ROWS}
+    row_off, ng, npt, ns = [0], 0, 0, 0
+    for bk in books:
+        a = {k: np.ascontiguousarray(bk[k], _BOOK_DT.get(k, np.uint64)) for k in L._BOOK_ROWS}
+        out["actor"].append(a["actor"].reshape(-1))
+        out["max"].append(a["max"])
+        out["gap_off"].append(a["gap_off"][:-1] + np.uint64(ng))
+        out["part_off"].append(a["part_off"][:-1] + np.uint64(npt))
+        out["psr_off"].append(a["psr_off"][:-1] + np.uint64(ns))
+        for k in ("gap_start", "gap_end", "part_version", "part_last_seq", "psr_start", "psr_end"):
+            out[k].append(a[k])
+        row_off.append(row_off[-1] + int(a["max"].size))
+        ng, npt, ns = ng + int(a["gap_off"][-1]), npt + int(a["part_off"][-1]), ns + int(a["psr_off"][-1])
+    for k, end in (("gap_off", ng), ("part_off", npt), ("psr_off", ns)):
+        out[k].append(np.array([end], np.uint64))
+    res = {k: np.concatenate(v).astype(_BOOK_DT.get(k, np.uint64)) for k, v in out.items()}
+    res["state_row_off"] = np.array(row_off, np.uint64)
+    return res
+
+
+class _StateEnc:
+    """corro_encode_states over one set of books: pass 0 on construction, pass 1 by write()."""
+
+    def __init__(self, engine, books, self_actors, ts, max_payload, device):
+        book = books if isinstance(books, dict) else concat_books(books)
+        F = int(book["state_row_off"].shape[0]) - 1
+        if isinstance(self_actors, (list, tuple)):
+            self_actors = np.frombuffer(b"".join(bytes(a) for a in self_actors), np.uint8)
+        if ts is None:
+            ts = [None] * F
+        has_ts = np.array([t is not None for t in ts], np.uint8)
+        tsv = np.array([(t or 0) for t in ts], np.uint64)
+        fields = dict(book, self_actor=self_actors, has_ts=has_ts, ts=tsv)
+        dts = dict(_BOOK_DT, self_actor=np.uint8, has_ts=np.uint8)
+        if device:
+            import torch
+            for k, a in fields.items():
+                if not hasattr(a, "is_cuda"):
+                    a = np.array(a, dts.get(k, np.uint64)).reshape(-1)     # (a copy: from_numpy wants it writable)
+                    fields[k] = torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a).cuda()
+                else:
+                    fields[k] = a.reshape(-1)
+        else:
+            fields = {k: np.ascontiguousarray(a, dts.get(k, np.uint64)).reshape(-1) for k, a in fields.items()}
+        r = L.StateEncIn()
+        for k, a in fields.items():
+            fields[k], p = engine._in_field(a, dts.get(k, np.uint64), device, k)
+            setattr(r, k, p)
+        count = (lambda a: int(a.numel())) if device else (lambda a: int(a.size))
+        r.nstates, r.nrows = F, count(fields["max"])
+        r.ngaps, r.nparts, r.npsr = count(fields["gap_start"]), count(fields["part_version"]), count(fields["psr_start"])
+        if count(fields["self_actor"]) != 16 * F or count(fields["has_ts"]) != F:
+            raise ValueError("one 16-byte self actor and one ts per state")
+        r.max_payload = max_payload
+        self.engine, self.fields, self.r, self.F = engine, fields, r, F
+        self.alloc, self.ptr, self.sync = engine._two_pass_io(device, fields["max"].device if device else None)
+        self.mem = L.CORRO_MEM_DEVICE if device else L.CORRO_MEM_HOST
+        self.o = L.StateEncOut()
+        res = {k: self.alloc(F + extra, dt) for k, dt, extra in _STATEENC_OUT}
+        for k, a in res.items():
+            setattr(self.o, k, self.ptr(a))
+        self._call(0)
+        self.head = {k: res[k][:F + extra] for k, _dt, extra in _STATEENC_OUT}
+        self.total_bytes = int(self.o.total_bytes)
+
+    def _call(self, which):
+        self.sync()
+        L.check(L.lib().corro_encode_states(self.engine._h, C.byref(self.r), self.mem, C.byref(self.o), which))
+
+    def write(self, buf=None):
+        """Pass 1 into `buf` (allocated here when None): the frames, total_bytes of them."""
+        if buf is None:
+            buf = self.alloc(self.total_bytes, np.uint8)
+        self.o.buf = self.ptr(buf)
+        self._call(1)
+        return buf[:self.total_bytes]
+
+
+def state_frames_from_books(engine, books, self_actors, ts=None, max_payload=0, device=False):
+    """corro_encode_states, both passes: sync books -> SyncMessageV1::State frames, one per state, back to
+    back. `books`: a list of Agent.sync_book() dicts, or one dict that already holds the shared row arrays
+    and "state_row_off" (concat_books; with device=True its arrays may be CUDA tensors, which are used
+    where they lie). self_actors: one 16-byte id per state; ts: None, or per state an int or None
+    (last_cleared_ts); max_payload: the codec's max_frame_length (0: 2^32 - 1). Host numpy arrays, or with
+    device=True CUDA tensors: then only the totals reach the host. Returns "buf" (uint8), "frame_off"
+    (nstates + 1), "state_status" (0, CORRO_E_INVALID for a book that is not canonical, CORRO_E_RANGE for a
+    payload above max_payload: such a state's frame is empty), "n_heads", "n_need", "n_partial" and
+    "total_bytes"."""
+    enc = _StateEnc(engine, books, self_actors, ts, max_payload, device)
+    res = dict(enc.head)
+    res["buf"], res["total_bytes"] = enc.write(), enc.total_bytes
+    return res
+
+
+def requests_from_books(engine, books, self_actors, sessions, ts=None, max_payload=0, chunk=10, drain=10):
+    """Sync books in, request bytes out, on the device: state_frames_from_books(device=True), then
+    requests_from_state_frames over its frames where they lie (sessions name states by index). Nothing is
+    read back in between but the totals."""
+    fr = state_frames_from_books(engine, books, self_actors, ts=ts, max_payload=max_payload, device=True)
+    res = requests_from_state_frames(engine, fr["buf"], fr["frame_off"], sessions, chunk, drain)
+    res["state_status"] = fr["state_status"]
+    return res
+
+
 def batch_compute_available_needs(engine, pairs):
     """compute_available_needs for many (ours, theirs) pairs in one kernel launch pair."""
     ent, index = entries_from_states(pairs)

@@ -723,6 +723,80 @@ typedef struct {
 } corro_sync_state;
 int corro_generate_sync(corro_bookie *bk, const uint8_t *self_actor, corro_sync_state *out, int pass);
 
+/* The bookie as one "sync book": what generate_sync reads, not what it computes. One row per actor of
+ * the bookie, in the order corro_generate_sync walks them, actors whose last() is None included
+ * (max = -1). Per row the needed() gaps as a CSR, and its partials as a CSR (versions ascending) with,
+ * per partial, last_seq and the seq ranges that are present -- the RangeInclusiveSet as stored, not its
+ * gaps, complete partials included. Pass 0 sets the four counts; pass 1 fills the arrays, or returns
+ * CORRO_E_INVALID and writes nothing when the bookie's counts are no longer the ones given. The arrays
+ * are the row arrays of corro_stateenc_in. */
+typedef struct {
+    uint64_t nrows, ngaps, nparts, npsr;               /* pass 0 output, pass 1 input */
+    uint8_t *actor;                                    /* 16 * nrows */
+    int64_t *max;                                      /* nrows: last(), -1 = None */
+    uint64_t *gap_off, *gap_start, *gap_end;           /* nrows + 1, ngaps, ngaps */
+    uint64_t *part_off, *part_version, *part_last_seq; /* nrows + 1, nparts, nparts */
+    uint64_t *psr_off, *psr_start, *psr_end;           /* nparts + 1, npsr, npsr */
+} corro_sync_book;
+int corro_bookie_sync_book(corro_bookie *bk, corro_sync_book *out, int pass);
+
+/* generate_sync on the device, and its encoding: nstates sync books -> nstates length-delimited
+ * SyncMessage::V1(SyncMessageV1::State) frames back to back in `buf`, in the layout stated at
+ * corro_statedec_in. State b's rows are [state_row_off[b], state_row_off[b + 1]) of one set of row
+ * arrays (corro_sync_book's) shared by all states.
+ *
+ * What a frame holds (sync.rs:284-333): a row with max = -1 contributes nothing; every other row gives
+ * a heads entry (actor, max), a need entry when its gap list is not empty, and a partial_need entry
+ * when at least one of its partials is included. A partial is included when it is not is_complete():
+ * when the complement of its present ranges (clipped to last_seq) within [1, last_seq] is not empty --
+ * the reference checks completeness over 1..=last_seq (agent.rs:1068-1074), so a partial that misses
+ * seq 0 alone, or one with last_seq = 0, counts as complete, here as in corro_generate_sync. An included
+ * partial is written as (version, the complement within [0, last_seq], ascending). The three maps are
+ * written in row order, one actor's versions ascending: the order Agent.generate_sync +
+ * wire.encode_sync_state give. last_cleared_ts is always written: u8 0, or u8 1 and the u64. No step
+ * computes an end + 1 that could wrap: last_seq and range ends of 2^64 - 1 are served.
+ *
+ * state_status[b]: 0 ok; CORRO_E_INVALID a book that is not canonical inside the state's rows -- gaps
+ * or present ranges that are inverted, unsorted, overlapping or touching, partial versions that do not
+ * strictly ascend, an offset array that decreases or passes its count (rows with max = -1 are held to
+ * the same form); CORRO_E_RANGE a payload larger than max_payload (the codec's max_frame_length; 0 and
+ * anything above 2^32 - 1 mean 2^32 - 1). CORRO_E_INVALID goes first. A state with a status other than
+ * 0 gets an empty frame (frame_off[b + 1] == frame_off[b]), zero counts, and affects no other state;
+ * the call returns 0.
+ *
+ * Two passes: pass 0 fills the per-state arrays and total_bytes, the caller allocates buf, pass 1
+ * sizes again and writes buf. `mem` covers every array of both structs; with CORRO_MEM_DEVICE only the
+ * totals cross PCIe. The call itself fails, before anything is written, with CORRO_E_INVALID for a
+ * state_row_off that decreases or passes nrows, for gap_off[nrows] != ngaps, part_off[nrows] != nparts
+ * or psr_off[nparts] != npsr (host arrays are screened before any device work), or for a pass-1
+ * total_bytes that differs from pass 0's; with CORRO_E_RANGE for 2^31 or more states, rows, gaps,
+ * partials or present ranges. Every payload is 1 mod 4 bytes long, so frames lie at every alignment.
+ * The merge state is not read; a poisoned context is served. */
+typedef struct {
+    uint64_t nstates;
+    const uint8_t *self_actor;                         /* 16 * nstates */
+    const uint8_t *has_ts;                             /* nstates: last_cleared_ts is Some */
+    const uint64_t *ts;                                /* nstates */
+    const uint64_t *state_row_off;                     /* nstates + 1 */
+    uint64_t nrows, ngaps, nparts, npsr;
+    const uint8_t *actor;                              /* 16 * nrows */
+    const int64_t *max;                                /* nrows, -1 = None */
+    const uint64_t *gap_off, *gap_start, *gap_end;     /* nrows + 1, ngaps, ngaps */
+    const uint64_t *part_off, *part_version, *part_last_seq; /* nrows + 1, nparts, nparts */
+    const uint64_t *psr_off, *psr_start, *psr_end;     /* nparts + 1, npsr, npsr */
+    uint64_t max_payload;
+} corro_stateenc_in;
+
+typedef struct {
+    uint64_t total_bytes;                              /* pass 0 output, pass 1 input */
+    int32_t *state_status;                             /* nstates (pass 0) */
+    uint64_t *frame_off;                               /* nstates + 1 (pass 0) */
+    uint32_t *n_heads, *n_need, *n_partial;            /* nstates each (pass 0): the three maps' sizes */
+    uint8_t *buf;                                      /* total_bytes (pass 1) */
+} corro_stateenc_out;
+
+int corro_encode_states(corro_ctx *ctx, const corro_stateenc_in *in, int mem, corro_stateenc_out *out, int pass);
+
 /* ------------------------------------------------------------------ wire decode */
 
 /* Decode length-delimited frames (tokio LengthDelimitedCodec: u32 big-endian length + payload,
