@@ -45,7 +45,7 @@ EXPORTS = [
     "corro_plan_requests", "corro_decode_requests", "corro_need_spans",
     "corro_need_tails", "corro_assemble_answers",
     "corro_bookie_buffered_index", "corro_buffered_spans", "corro_assemble_answers_buffered",
-    "corro_decode_states", "corro_bookie_sync_book", "corro_encode_states",
+    "corro_decode_states", "corro_bookie_sync_book", "corro_encode_states", "corro_match_changes",
 ]
 
 CORRO_CS_FULL, CORRO_CS_EMPTY, CORRO_CS_EMPTY_SET = 0, 1, 2
@@ -282,6 +282,17 @@ class StateEncOut(C.Structure):
         "state_status", "frame_off", "n_heads", "n_need", "n_partial", "buf")]
 
 
+class MatchIn(C.Structure):
+    _fields_ = [("n", C.c_uint64)] + [(k, C.c_void_p) for k in ("pk", "table_cid", "cl", "impactful")] + [
+        ("ncs", C.c_uint64), ("cs", C.c_void_p), ("nclasses", C.c_uint32), ("nslots", C.c_uint32),
+        ("col_class_bits", C.c_void_p)]
+
+
+class MatchOut(C.Structure):
+    _fields_ = [("ncand", C.c_uint64)] + [(k, C.c_void_p) for k in (
+        "class_off", "cand_change", "cand_cs", "cand_table", "cand_pk", "cand_cl")]
+
+
 _lib = None
 
 
@@ -383,6 +394,7 @@ def lib():
         "corro_generate_sync": (i32, [vp, vp, C.POINTER(SyncState), i32]),
         "corro_bookie_sync_book": (i32, [vp, C.POINTER(SyncBook), i32]),
         "corro_encode_states": (i32, [vp, C.POINTER(StateEncIn), i32, C.POINTER(StateEncOut), i32]),
+        "corro_match_changes": (i32, [vp, C.POINTER(MatchIn), i32, C.POINTER(MatchOut), i32]),
         "corro_partition_ranks": (i32, [vp, C.POINTER(Changes), u32, C.POINTER(Changes), vp]),
         "corro_packed_record_bytes": (i32, [C.POINTER(Changes), vp]),
         "corro_partition_packed": (i32, [vp, C.POINTER(Changes), u32, vp, vp, vp]),

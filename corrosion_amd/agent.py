@@ -317,7 +317,8 @@ class Agent:
         they lie (CORRO_MEM_DEVICE_HEADERS: no change or header crosses PCIe again; the known
         outcomes come back once). Frames with a non-zero decode status are not applied. Returns
         (Processed over the applied frames, with .impact = per-change impactful flags as a CUDA
-        uint8 tensor, per-frame decode status)."""
+        uint8 tensor and .dec = the decode they index (what match_changes takes), per-frame decode
+        status)."""
         import torch
         dec = self.engine.decode_frames(buf, payload, device=True, device_headers=True)
         nk = dec["n_dev"]
@@ -341,8 +342,19 @@ class Agent:
                                                        nk, C.byref(s), L.CORRO_MEM_DEVICE_HEADERS, C.byref(out)))
         res = Processed(known=[L.KNOWN.get(int(k), int(k)) for k in known[:nk].cpu().tolist()])
         res.impact = imp[:n]
+        res.dec = dec
         res.ready = self.take_ready()
         return res, dec["status"]
+
+    def match_changes(self, processed, dec, filters):
+        """match_changes for the subscription and update filters (updates.MatchFilters) behind
+        process_frames, on the device: `processed` is its Processed (with .impact), `dec` the decode it ran
+        on (processed.dec). The batch columns, the kept
+        frames' headers and the impact flags are read where they lie (util.rs:1026-1030). Returns
+        updates.match_changes' result; cand_cs indexes the kept frames (dec["cs_dev"])."""
+        from . import updates
+        return updates.match_changes(self.engine, dec["changes"], processed.impact, dec["cs_dev"], filters, device=True,
+                                     ncs=dec["n_dev"])
 
     def take_ready(self):
         c = C.c_uint64()

@@ -303,6 +303,11 @@ struct corro_ctx {
     // state encode (state_encode.hip): [0] staged host inputs, the per-gap / per-partial / per-row /
     // per-state sizes, their scans and rocPRIM temp, [1] staged host outputs
     corro::DevBuf d_stateenc[2];
+    // change matching (match.hip): [0] staged host inputs, the per-changeset and per-change columns, class_off
+    // and rocPRIM temp, [1] the per-match columns, the slot table and the sort's temp, [2] staged host outputs
+    corro::DevBuf d_match[3];
+    corro::DevBuf d_match_base;   // u32 per table (+ 1): its first column slot
+    bool match_base_ready = false;
     bool wire_schema_ready = false;
     const uint8_t *wire_names = nullptr;
     const uint32_t *wire_toff = nullptr, *wire_tlen = nullptr, *wire_tbase = nullptr, *wire_tn = nullptr,

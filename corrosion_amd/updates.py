@@ -1,0 +1,227 @@
+"""match_changes for subscriptions and update handles over the device engine.
+
+Mirrors corro-types/src/updates.rs: `match_changes` (:420-481) with the two `filter_matchable_change`
+(a subscription's, pubsub.rs:294-332, and an update handle's, updates.rs:92-121), `handle_candidates`
+(:270-305) and `match_changes_from_db_version` (:483-536). The filter, the first-occurrence dedup and
+the compaction run in libcorro_hip.so (csrc/match.hip, corro_match_changes) over the arrays a
+process_multiple_changes call left on the device; this module resolves names into the bit matrix the
+kernel reads and turns the candidate columns back into per-handle maps.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib as L
+from .engine import _is_torch
+
+SENTINEL = "-1"
+UPDATE, DELETE = "Update", "Delete"
+_CS_WORDS = C.sizeof(L.Changeset) // 8
+_CS_OFF, _CS_COUNT = L.Changeset.change_off.offset // 8, L.Changeset.change_count.offset // 8
+
+
+class MatchFilters:
+    """The live handles as filter classes. engine: a MergeEngine, or its schema {table: [columns]} in table
+    order. subs: one {table: [columns]} per subscription (its query's table_columns); updates: one table
+    name per update handle. Handles are numbered subs first, then updates. A filter is a set of column
+    slots -- slot(t, cid) = base[t] + cid, cid 0 the row sentinel -- and handles with equal sets share one
+    class: `handle_class[h]`, `nclasses`, and `bits`, the nslots x ceil(nclasses / 32) uint32 matrix of
+    corro_match_in.col_class_bits. An unknown table or column is a ValueError."""
+
+    def __init__(self, engine, subs=(), updates=()):
+        schema = engine.schema if hasattr(engine, "schema") else list(dict(engine).items())
+        self.tables = [name for name, _cols in schema]
+        cols = {name: list(c) for name, c in schema}
+        self.base = {}
+        at = 0
+        for name in self.tables:
+            self.base[name] = at
+            at += len(cols[name]) + 1
+        self.nslots = at
+        self.handles = [("sub", {t: list(c) for t, c in s.items()}) for s in subs] + [("update", t) for t in updates]
+        classes = {}
+        self.handle_class = []
+        for kind, what in self.handles:
+            slots = set()
+            for table, names in (what.items() if kind == "sub" else [(what, None)]):
+                if table not in cols:
+                    raise ValueError(f"no such table: {table}")
+                if names is None:                       # an update handle takes every change of its table
+                    slots.update(range(self.base[table], self.base[table] + len(cols[table]) + 1))
+                    continue
+                slots.add(self.base[table])             # the sentinel passes any subscription naming the table
+                for c in names:
+                    if c == SENTINEL:
+                        continue
+                    if c not in cols[table]:
+                        raise ValueError(f"no such column: {table}.{c}")
+                    slots.add(self.base[table] + 1 + cols[table].index(c))
+            self.handle_class.append(classes.setdefault(frozenset(slots), len(classes)))
+        self.nclasses = len(classes)
+        if self.nclasses >= 1 << 16:
+            raise L.CorroError(-6, "at most 2^16 - 1 filter classes")
+        self.words = (self.nclasses + 31) // 32
+        self.bits = np.zeros((self.nslots, self.words), np.uint32)
+        for slots, c in classes.items():
+            for s in slots:
+                self.bits[s, c // 32] |= np.uint32(1 << (c % 32))
+        self._dev = {}
+
+    def device_bits(self, device):
+        """The matrix as a CUDA tensor, uploaded once per device."""
+        import torch
+        key = str(device)
+        if key not in self._dev:
+            self._dev[key] = torch.from_numpy(self.bits.view(np.int32).reshape(-1).copy()).to(device)
+        return self._dev[key]
+
+
+def _cs_records(cs, ncs, on_dev, dev):
+    """cs as corro_changeset records: a ctypes Changeset array / uint8 record buffer is used as it is;
+    an (ncs, 2) array of (change_off, change_count) becomes records that hold nothing else."""
+    if isinstance(cs, C.Array):
+        if on_dev:
+            raise ValueError("device matching takes its changeset headers as a CUDA tensor")
+        return cs, (len(cs) if ncs is None else ncs), C.addressof(cs)
+    if on_dev:
+        import torch
+        if not _is_torch(cs) or not cs.is_cuda:
+            raise ValueError("device matching takes its changeset headers as a CUDA tensor")
+        if cs.dtype == torch.uint8:
+            have = int(cs.numel()) // C.sizeof(L.Changeset)
+            ncs = have if ncs is None else ncs
+            if ncs > have or not cs.is_contiguous():
+                raise ValueError("cs holds fewer corro_changeset records than ncs")
+            return cs, ncs, cs.data_ptr()
+        pairs = cs.reshape(-1, 2).to(torch.int64)
+        rec = torch.zeros((max(1, pairs.shape[0]), _CS_WORDS), dtype=torch.int64, device=dev)
+        rec[:pairs.shape[0], _CS_OFF] = pairs[:, 0]
+        rec[:pairs.shape[0], _CS_COUNT] = pairs[:, 1]
+        return rec, int(pairs.shape[0]) if ncs is None else ncs, rec.data_ptr()
+    a = np.asarray(cs)
+    if a.dtype == np.uint8 and a.ndim == 1:
+        a = np.ascontiguousarray(a)
+        have = a.size // C.sizeof(L.Changeset)
+        return a, (have if ncs is None else ncs), a.ctypes.data
+    pairs = a.reshape(-1, 2).astype(np.uint64)
+    rec = np.zeros((max(1, pairs.shape[0]), _CS_WORDS), np.uint64)
+    rec[:pairs.shape[0], _CS_OFF] = pairs[:, 0]
+    rec[:pairs.shape[0], _CS_COUNT] = pairs[:, 1]
+    return rec, (int(pairs.shape[0]) if ncs is None else ncs), rec.ctypes.data
+
+
+_OUT = (("cand_change", np.uint32), ("cand_cs", np.uint32), ("cand_table", np.uint32), ("cand_pk", np.uint64),
+        ("cand_cl", np.uint32))
+
+
+def match_changes(engine, changes, impactful, cs, filters, device=None, ncs=None, timings=None):
+    """corro_match_changes, both passes. changes: the batch columns "pk", "table_cid", "cl" (others are
+    ignored); impactful: one uint8 flag per change (Processed.impact); cs: the changeset headers -- a
+    buffer of corro_changeset records (decode_frames' "cs_dev", a ctypes array on the host) or an
+    (ncs, 2) array of (change_off, change_count) -- of which the first `ncs` count. CUDA tensors
+    (device=True; nothing but totals reaches the host) or numpy arrays (device=False); None decides by
+    the type of changes["pk"]. Returns "ncand", "class_off" (nclasses + 1) and the candidate columns
+    "cand_change", "cand_cs", "cand_table", "cand_pk", "cand_cl" in the same memory: class c's candidates
+    are [class_off[c], class_off[c + 1]) in ascending change index. timings: a dict that receives
+    "pass0_ms" / "pass1_ms", the wall time of each call (a call returns with its stream idle)."""
+    import time
+    lib = L.lib()
+    on_dev = _is_torch(changes["pk"]) if device is None else bool(device)
+    dev = changes["pk"].device if on_dev else None
+    n = int(changes["pk"].shape[0])
+    s = L.MatchIn()
+    s.n = n
+    keep = []
+    for k, src, dt in (("pk", changes["pk"], np.uint64), ("table_cid", changes["table_cid"], np.uint32),
+                       ("cl", changes["cl"], np.uint32), ("impactful", impactful, np.uint8)):
+        a, p = engine._in_field(src, dt, on_dev, k, n)
+        keep.append(a)
+        setattr(s, k, p)
+    rec, ncs, p = _cs_records(cs, ncs, on_dev, dev)
+    s.ncs, s.cs = ncs, (p if ncs else None)
+    s.nclasses, s.nslots = filters.nclasses, filters.nslots
+    bits = filters.device_bits(dev) if on_dev else filters.bits
+    if (int(bits.numel()) if on_dev else bits.size):
+        s.col_class_bits = bits.data_ptr() if on_dev else bits.ctypes.data
+    alloc, ptr, sync = engine._two_pass_io(on_dev, dev)
+    mem = L.CORRO_MEM_DEVICE if on_dev else L.CORRO_MEM_HOST
+    o = L.MatchOut()
+    class_off = alloc(filters.nclasses + 1, np.uint64)
+    o.class_off = ptr(class_off)
+    sync()
+    t0 = time.perf_counter()
+    L.check(lib.corro_match_changes(engine._h, C.byref(s), mem, C.byref(o), 0))
+    t1 = time.perf_counter()
+    ncand = int(o.ncand)
+    res = {k: alloc(ncand, dt) for k, dt in _OUT}
+    for k, a in res.items():
+        setattr(o, k, ptr(a))
+    sync()
+    t2 = time.perf_counter()
+    L.check(lib.corro_match_changes(engine._h, C.byref(s), mem, C.byref(o), 1))
+    if timings is not None:
+        timings["pass0_ms"], timings["pass1_ms"] = (t1 - t0) * 1e3, (time.perf_counter() - t2) * 1e3
+    res = {k: a[:ncand] for k, a in res.items()}
+    res["class_off"], res["ncand"] = class_off[:filters.nclasses + 1], ncand
+    return res
+
+
+def _host(a, dt):
+    if _is_torch(a):
+        a = a.cpu().numpy()
+    return np.ascontiguousarray(a).view(dt)
+
+
+def candidates_by_class(result, filters):
+    """Per class the list of (changeset index, {table name: {pk key: cl}}) for the changesets with at
+    least one candidate, in order; the dicts are insertion-ordered like the reference's IndexMaps."""
+    off = _host(result["class_off"], np.uint64).tolist()
+    cs = _host(result["cand_cs"], np.uint32).tolist()
+    table = _host(result["cand_table"], np.uint32).tolist()
+    pk = _host(result["cand_pk"], np.uint64).tolist()
+    cl = _host(result["cand_cl"], np.uint32).tolist()
+    out = []
+    for c in range(filters.nclasses):
+        per = []
+        for j in range(off[c], off[c + 1]):
+            if not per or per[-1][0] != cs[j]:
+                per.append((cs[j], {}))
+            per[-1][1].setdefault(filters.tables[table[j]], {})[pk[j]] = cl[j]
+        out.append(per)
+    return out
+
+
+def candidates_by_handle(result, filters):
+    """Per handle (subs first, then updates) what match_changes sends it: a list of (changeset index,
+    MatchCandidates) over the changesets that gave it a candidate. Handles of one class share their list."""
+    per_class = candidates_by_class(result, filters)
+    return [per_class[c] for c in filters.handle_class]
+
+
+def notify_events(result, filters):
+    """handle_candidates over candidates_by_handle: per handle a list of (changeset index, [(Update |
+    Delete, pk key)]), an even cl a Delete and any other an Update, tables then pks in map order."""
+    return [[(s, [(DELETE if cl % 2 == 0 else UPDATE, pk) for pks in cands.values() for pk, cl in pks.items()])
+             for s, cands in per] for per in candidates_by_handle(result, filters)]
+
+
+def match_extracted(engine, rows, filters):
+    """match_changes_from_db_version (updates.rs:483-536), the form process_fully_buffered_changes calls
+    (util.rs:668-684): `rows` are the crsql_changes rows of one extract_changes group in seq order ("pk",
+    "table_cid", "cl"; CUDA tensors, or numpy arrays that are uploaded). They run as one changeset with
+    every flag 1; cl (int64 in extracted rows) is cast to u32 on the device. Returns match_changes' result
+    on the device."""
+    import torch
+    cols = {}
+    for k in ("pk", "table_cid", "cl"):
+        a = rows[k]
+        if not _is_torch(a):
+            a = np.ascontiguousarray(a)
+            a = torch.from_numpy(a.view({8: np.int64, 4: np.int32}[a.dtype.itemsize])).to(f"cuda:{engine.device}")
+        cols[k] = a.contiguous()
+    cols["cl"] = cols["cl"].to(torch.int32)
+    n = int(cols["pk"].shape[0])
+    dev = cols["pk"].device
+    imp = torch.ones(n, dtype=torch.uint8, device=dev)
+    cs = torch.tensor([[0, n]], dtype=torch.int64, device=dev)
+    return match_changes(engine, cols, imp, cs, filters, device=True)

@@ -1334,6 +1334,76 @@ typedef struct {
 int corro_assemble_answers_buffered(corro_ctx *ctx, const corro_assemble_buffered_in *in, int mem, corro_assembled *out,
                                     int pass);
 
+/* ------------------------------------------------------------------ match_changes */
+
+/* match_changes (corro-types/src/updates.rs:420-481) for the subscriptions and the update handles,
+ * the last per-change loop of process_multiple_changes (corro-agent/src/agent/util.rs:1026-1030), over
+ * the arrays that call left on the device: out->impactful of corro_process_multiple_changes and the pk /
+ * table_cid / cl columns of its batch. No other column is read.
+ *
+ * Filters are given as classes. A class is one distinct filter, a set of (table, cid) pairs; the caller
+ * folds handles with equal filters into one class. filter_matchable_change of a subscription
+ * (pubsub.rs:294-332) on {table: cols} is the row sentinel (cid 0) and the listed cids of each named
+ * table; that of an update handle (updates.rs:92-121) is every cid of its one table. Column slot
+ * slot(t, cid) = base[t] + cid with base[t] = the sum over u < t of (ncols_u + 1); nslots is the schema's
+ * total. col_class_bits holds nslots x ceil(nclasses / 32) u32 words: per slot the bitset of the classes
+ * that take a change of that column (bit c % 32 of word c / 32; bits at nclasses and above are ignored).
+ *
+ * Change i of changeset s is a candidate of class c iff impactful[i] != 0, bit c of its slot's words is
+ * set, and no j < i of the same changeset with the same (table_cid >> 16, pk) satisfies both: both filters
+ * skip a pk already in the map, so the candidate of a (changeset, class, table, pk) is the first taken
+ * change, and cand_cl is that change's cl (handle_candidates, updates.rs:270-305: an even cl is a
+ * Delete, any other an Update). Deduplication is per changeset. A change that lies in no changeset's
+ * range, one with table_cid == CORRO_TCID_UNKNOWN, a table index the schema does not have or a cid above
+ * its table's is never a candidate and never indexes the matrix. A change whose flag is 0 does not exist
+ * for matching: that covers every changeset that was skipped, cleared, partial or rolled back.
+ *
+ * cs: only change_off and change_count are read. The non-empty ranges must ascend and be disjoint in cs
+ * order and lie inside the batch (what corro_decode_frames' cs_dev and the agent produce); a change
+ * finds its changeset by binary search, and ascending change index is changeset order, then vector order.
+ *
+ * Output: class c's candidates are [class_off[c], class_off[c + 1]) in ascending cand_change. Inserted
+ * in that order into an IndexMap<table, IndexMap<pk, cl>> per cand_cs they reproduce, for every
+ * changeset, the MatchCandidates match_changes sends to a handle of that class, tables and pks in the
+ * same first-appearance order; class_off[c + 1] - class_off[c] is what the reference adds to matched_count.
+ * Rows are keyed by the engine's pk key, as everywhere else: two non-canonical encodings of one interned
+ * pk are one candidate here and two in the reference (corro_pk_keys' documented behaviour).
+ *
+ * Two passes: pass 0 gives ncand and class_off, the caller allocates, pass 1 computes everything again
+ * and fills the five candidate columns. `mem` (CORRO_MEM_HOST or CORRO_MEM_DEVICE) covers every array of
+ * both structs; with CORRO_MEM_DEVICE only totals cross PCIe. The call fails, before anything is
+ * written, with CORRO_E_INVALID for a NULL struct, a bad mem or pass, a required array that is NULL
+ * while its count is not 0, changeset ranges that break the rule above (host arrays are screened on the
+ * host, device arrays on the device), an nslots that is not the schema's, or a pass-1 ncand that differs
+ * from what pass 1 computes; with CORRO_E_RANGE for n, ncs or the number of (change, class) matches at
+ * 2^31 or more, or nclasses at 2^16 or more; with CORRO_E_NO_DEVICE, after the argument screen, when no
+ * device is usable. n, ncs or nclasses of 0 give ncand = 0 and a closed class_off. The merge state is
+ * not read; a poisoned context is served. */
+typedef struct {
+    uint64_t n;
+    const uint64_t *pk;                    /* n: corro_changes.pk */
+    const uint32_t *table_cid;             /* n */
+    const uint32_t *cl;                    /* n */
+    const uint8_t *impactful;              /* n: corro_process_out.impactful as it is */
+    uint64_t ncs;
+    const corro_changeset *cs;             /* ncs, in `mem`'s memory */
+    uint32_t nclasses;
+    uint32_t nslots;
+    const uint32_t *col_class_bits;        /* nslots * ceil(nclasses / 32) */
+} corro_match_in;
+
+typedef struct {
+    uint64_t ncand;                        /* pass 0 output, pass 1 input */
+    uint64_t *class_off;                   /* nclasses + 1 (pass 0) */
+    uint32_t *cand_change;                 /* ncand each (pass 1): index into the batch */
+    uint32_t *cand_cs;                     /* index into cs */
+    uint32_t *cand_table;                  /* table_cid >> 16 */
+    uint64_t *cand_pk;
+    uint32_t *cand_cl;
+} corro_match_out;
+
+int corro_match_changes(corro_ctx *ctx, const corro_match_in *in, int mem, corro_match_out *out, int pass);
+
 #ifdef __cplusplus
 }
 #endif
