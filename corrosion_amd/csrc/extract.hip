@@ -217,6 +217,16 @@ __device__ inline uint64_t lower_bound64(const uint64_t *a, uint64_t n, uint64_t
     }
     return lo;
 }
+// first index whose key is > v (v's successor may not exist: v can be all ones)
+__device__ inline uint64_t upper_bound64(const uint64_t *a, uint64_t n, uint64_t v) {
+    uint64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint64_t mid = (lo + hi) >> 1;
+        if (a[mid] <= v) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
 __device__ inline uint32_t lower_bound32(const uint32_t *a, uint32_t lo, uint32_t hi, uint64_t v) {
     while (lo < hi) {
         const uint32_t mid = (lo + hi) >> 1;
@@ -237,7 +247,9 @@ __device__ inline void need_slice(const XIndex &x, const XParams &p, const XNeed
     if (t > p.max_dbv) t = p.max_dbv;
     const uint64_t base = (uint64_t)site << p.db;
     lo = lower_bound64(x.hkey, p.m, base | s);
-    hi = lower_bound64(x.hkey, p.m, (base | t) + 1);
+    // (not a lower bound on (base | t) + 1: at db + stb == 64 the highest site's key at max_dbv is all
+    // ones and its successor wraps to 0, which emptied every need reaching that version)
+    hi = upper_bound64(x.hkey, p.m, base | t);
 }
 
 __global__ void k_xcount(XIndex x, XParams p, XNeeds nd, uint64_t *gcnt, uint64_t *rcnt) {

@@ -450,6 +450,9 @@ class Booked:
         return bool(lib().of_booked_contains(self._h, v))
 
 
+I64_MAX = (1 << 63) - 1
+
+
 def extract_changes(rows, needs):
     """Changeset extraction on exported crsql_changes rows (numpy restatement of handle_need's two
     queries, corro-agent/src/api/peer/mod.rs:385-394 and :423-431 / :603-611): per need, the
@@ -464,6 +467,12 @@ def extract_changes(rows, needs):
     out = []
     for e in range(len(needs["site"])):
         a, s0, e0 = int(needs["site"][e]), int(needs["start"][e]), int(needs["end"][e])
+        # bounds are u64, db_versions int64: searched as given, a bound >= 2^63 promotes the comparison
+        # to float64, where 2^63 - 1 == 2^63 (a need starting at 2^63 then found version 2^63 - 1)
+        if s0 > e0 or s0 > I64_MAX:
+            out.append([])
+            continue
+        e0 = min(e0, I64_MAX)
         lo = np.searchsorted(ks, a, "left")
         hi = np.searchsorted(ks, a, "right")
         sub = order[lo:hi]

@@ -1,39 +1,20 @@
 """GPU parity of the sync server's changeset extraction (corro_extract_changes, csrc/extract.hip)
 against the oracle restatement of handle_need's two queries (oracle.extract_changes over the
 exported crsql_changes rows), and handle_need end to end (corrosion_amd/serve.py) on an agent
-state built through process_multiple_changes. Bar: identical versions (DESC), MAX(seq), MAX(ts)
-and rows (seq ASC; ties on seq compared as a set, the SQL leaves their order open)."""
+state built through process_multiple_changes. Bar (tests/extract_util.py check_extract, the one
+checker of every extraction test): identical counts, versions (DESC), MAX(seq), MAX(ts), groups that
+tile each need's row range, and rows in seq ASC order AS EMITTED (only rows of equal (version, seq)
+may permute: the SQL leaves the order of ties open). tests/test_gpu_extract_edges.py holds the
+directed cases."""
 import numpy as np
 import pytest
 
 import synth
 from oracle import oracle as O
+from tests.extract_model import from_oracle
+from tests.extract_util import check_extract, device_needs
 
 pytestmark = pytest.mark.gpu
-
-ROWF = ("pk", "table_cid", "col_version", "db_version", "cl", "seq", "site", "ts", "val0", "val1", "val_type",
-        "val_len")
-
-
-def _rows_tuple(rows, idx):
-    t = [tuple(int(rows[k][i]) for k in ROWF) for i in idx]
-    return sorted(t, key=lambda r: (r[5], r[1], r[0]))
-
-
-def got_groups(res, e):
-    from corrosion_amd.engine import ROW_FIELDS
-    # device results come back as signed torch dtypes: view them in the row field types
-    rows = {k: (v.cpu().numpy().view(ROW_FIELDS[k]) if hasattr(v, "cpu") else v) for k, v in res["rows"].items()}
-    R = {k: (v.cpu().numpy() if hasattr(v, "cpu") else v) for k, v in res.items() if k != "rows"}
-    out = []
-    for g in range(int(R["grp_off"][e]), int(R["grp_off"][e + 1])):
-        ro, rn = int(R["grp_row_off"][g]), int(R["grp_rows"][g])
-        out.append((int(R["version"][g]), int(R["last_seq"][g]), int(R["ts"][g]), _rows_tuple(rows, range(ro, ro + rn))))
-    return out
-
-
-def exp_groups(rows, groups):
-    return [(v, last, ts, _rows_tuple(rows, g)) for v, last, ts, g in groups]
 
 
 def random_needs(rng, n, nsites, max_dbv, seq_filter):
@@ -79,23 +60,21 @@ def test_extract_vs_oracle(kind, seq_filter):
     rng = np.random.default_rng(7)
     nd = random_needs(rng, 3000, 8, int(b["db_version"].max()), seq_filter)
     res = e.extract_changes(nd)
-    exp = O.extract_changes(rows, nd)
-    for i in range(len(nd["site"])):
-        assert got_groups(res, i) == exp_groups(rows, exp[i]), i
+    check_extract(res, from_oracle(rows, O.extract_changes(rows, nd)), nd)
 
 
 def test_extract_device_needs_equal_host_needs():
-    import torch
     sites = synth.site_ids(8, 3)
     b = synth.uniform_batch(40000, 8, 3000, 4, 43)
     e = _engine({"t": ["a", "b", "c", "d"]}, sites)
     e.apply(b)
     nd = random_needs(np.random.default_rng(8), 2000, 8, int(b["db_version"].max()), True)
-    host = e.extract_changes(nd)
-    dev = e.extract_changes({k: torch.from_numpy(v.view(np.int64) if v.dtype == np.uint64 else v.view(np.int32)).cuda()
-                             for k, v in nd.items()})
-    for i in range(0, 2000, 7):
-        assert got_groups(dev, i) == got_groups(host, i)
+    rows = e.export()
+    exp = from_oracle(rows, O.extract_changes(rows, nd))
+    check_extract(e.extract_changes(nd), exp, nd)
+    dev = e.extract_changes(device_needs(nd))
+    assert all(v.is_cuda for v in dev["rows"].values()) and dev["version"].is_cuda
+    check_extract(dev, exp, nd)
 
 
 def test_extract_two_sort_path_large_versions():
@@ -113,9 +92,8 @@ def test_extract_two_sort_path_large_versions():
           "start": np.array([lo, lo + 3, lo, lo + 40, lo + 1], np.uint64),
           "end": np.array([lo + 5, lo + 3, lo + 100, lo + 41, lo + 1], np.uint64)}
     res = e.extract_changes(nd)
-    exp = O.extract_changes(rows, nd)
-    for i in range(5):
-        assert got_groups(res, i) == exp_groups(rows, exp[i])
+    exp = from_oracle(rows, O.extract_changes(rows, nd))
+    check_extract(res, exp, nd)
     assert sum(len(g) for g in exp) > 0
 
 
@@ -128,8 +106,10 @@ def test_extract_edge_cases_and_index_refresh():
     assert int(res["grp_off"][-1]) == 0 and int(res["row_off"][-1]) == 0
     b1 = synth.uniform_batch(5000, 4, 500, 4, 45)
     e.apply(b1)
-    r1 = e.extract_changes(nd)
-    assert got_groups(r1, 1) == []                  # unknown site ordinal
+    rows1 = e.export()
+    exp1 = from_oracle(rows1, O.extract_changes(rows1, nd))
+    assert exp1[0] != [] and exp1[1] == []          # unknown site ordinal
+    check_extract(e.extract_changes(nd), exp1, nd)
     b2 = synth.uniform_batch(5000, 4, 500, 4, 46)
     b2["db_version"] = b2["db_version"] + 1000
     e.apply(b2)                                      # new state epoch: index rebuilt
@@ -137,9 +117,7 @@ def test_extract_edge_cases_and_index_refresh():
     nd2 = {"site": np.array([0, 1, 2, 3], np.uint32), "start": np.array([1, 990, 1000, 0], np.uint64),
            "end": np.array([2000, 1010, 1000, 0], np.uint64)}
     res = e.extract_changes(nd2)
-    exp = O.extract_changes(rows, nd2)
-    for i in range(4):
-        assert got_groups(res, i) == exp_groups(rows, exp[i])
+    check_extract(res, from_oracle(rows, O.extract_changes(rows, nd2)), nd2)
     e.reset()
     assert int(e.extract_changes(nd2)["grp_off"][-1]) == 0
 
