@@ -123,16 +123,17 @@ def flatten(sessions, site_of):
 
 def expected(sessions, groups, chunk=10, drain=10):
     """What corro_plan_requests must return for flatten()'s arrays: per group the joined frame bytes,
-    and the frame table columns over all groups."""
+    the frame table columns over all groups, and the groups' frame offsets."""
     plans = [plan_session(s, chunk, drain) for s in sessions]
-    bufs, entry, rnd, needs = [], [], [], []
+    bufs, entry, rnd, needs, gfo = [], [], [], [], [0]
     for sn, sv, e0 in groups:
         fr = plans[sn][sv]
         bufs.append(b"".join(frame_bytes(a, nds) for _r, _e, a, nds in fr))
         entry += [e0 + e for _r, e, _a, _n in fr]
         rnd += [r for r, _e, _a, _n in fr]
         needs += [len(n) for _r, _e, _a, n in fr]
-    return {"group_bytes": bufs, "frame_entry": entry, "frame_round": rnd, "frame_needs": needs}
+        gfo.append(len(entry))
+    return {"group_bytes": bufs, "frame_entry": entry, "frame_round": rnd, "frame_needs": needs, "grp_frame_off": gfo}
 
 
 ACTORS = [bytes([16 * k + i for i in range(16)]) for k in range(4)]
@@ -164,3 +165,33 @@ def random_session(rng, max_ver=150):
 def random_sessions(count=300, seed=20240):
     rng = np.random.default_rng(seed)
     return [random_session(rng) for _ in range(count)]
+
+
+def tile_edge_sessions():
+    """The sessions of the output-tile test: one Partial of 600 shuffled disjoint ranges (a 9,652-byte
+    frame), 400 one-need Full frames, and a server whose frames fill 8192 bytes exactly."""
+    A0 = ACTORS[0]
+    rng = np.random.default_rng(9)
+    ranges = [(20 * k, 20 * k + 7) for k in range(600)]
+    shuffled = tuple(ranges[i] for i in rng.permutation(600))
+    big = [[(A0, [("P", 3, shuffled)])]]
+    many = [[(A0, [("F", 20 * k, 20 * k + 3) for k in range(400)])]]
+    # 143 one-piece Full frames (56 bytes) and Partials of two and three ranges (84 and 100 bytes) fill
+    # 8192 bytes exactly: the second group's first frame starts on the tile edge
+    edge = [[(A0, [("P", 9, ((1, 2), (4, 5))), ("P", 8, ((1, 2), (4, 5), (7, 8)))] +
+              [("F", 20 * k, 20 * k + 3) for k in range(143)])],
+            [(ACTORS[1], [("F", 1, 5), ("P", 2, ((0, 0),))])]]
+    return big, many, edge
+
+
+def quirk_sessions():
+    """The sessions of the quirk test, one oddity of the reference's loop each."""
+    A0 = ACTORS[0]
+    return [
+        [[(A0, [("F", 1, 21)])]],                                   # (e - s) % chunk == 0: a trailing one-version chunk
+        [[(A0, [("F", 9, 3), ("F", 4, 4)])], [(A0, [("F", 7, 2)])]],  # s > e: no item; a server left without items
+        [[(A0, [("P", 5, ()), ("P", 6, ((3, 3),))])]],               # an empty seq list: no frame
+        [[(A0, [("P", 5, ((0, 4), (5, 9)))])]],                       # adjacent seqs merge
+        [[(A0, [("F", 1, 30), ("P", 2, ((0, 9),))])], [(A0, [("F", 5, 25), ("P", 2, ((2, 3), (9, 9)))])],
+         [(ACTORS[2], [("F", 1, 3)])]],                            # a server all of whose items are deduped away
+    ]

@@ -40,8 +40,8 @@ def to_dev(arr):
     return {k: torch.from_numpy(np.ascontiguousarray(v).view(view[v.dtype])).cuda() for k, v in arr.items()}
 
 
-def plan(arr, chunk, drain, mem):
-    res = S._plan_requests(engine(), to_dev(arr) if mem == "device" else arr, chunk, drain, mem == "device")
+def plan(arr, chunk, drain, mem, eng=None):
+    res = S._plan_requests(eng or engine(), to_dev(arr) if mem == "device" else arr, chunk, drain, mem == "device")
     return {k: (v.cpu().numpy() if hasattr(v, "cpu") else v) for k, v in res.items()}
 
 
@@ -52,7 +52,7 @@ def check(res, want, ngroups):
     buf = res["buf"].tobytes()
     for g, wb in enumerate(want["group_bytes"]):
         assert buf[fo[gfo[g]]:fo[gfo[g + 1]]] == wb, f"group {g}"
-    for k in ("frame_entry", "frame_round", "frame_needs"):
+    for k in ("frame_entry", "frame_round", "frame_needs", "grp_frame_off"):
         assert res[k].astype(np.int64).tolist() == want[k], k
 
 
@@ -119,20 +119,11 @@ def test_hot_group_identical_huge_needs(mem):
 
 @pytest.mark.parametrize("mem", MEMS)
 def test_tile_edges(mem):
-    rng = np.random.default_rng(9)
-    ranges = [(20 * k, 20 * k + 7) for k in range(600)]
-    shuffled = tuple(ranges[i] for i in rng.permutation(600))
-    big = [[(A0, [("P", 3, shuffled)])]]
+    big, many, edge = U.tile_edge_sessions()
     res = run_sessions([big], 10, 10, mem)
     assert res["nbytes"] == 9648 + 4
-    many = [[(A0, [("F", 20 * k, 20 * k + 3) for k in range(400)])]]
     res = run_sessions([many], 10, 10, mem)
     assert res["nframes"] == 400 and list(res["frame_needs"]) == [1] * 400
-    # 143 one-piece Full frames (56 bytes) and Partials of two and three ranges (84 and 100 bytes) fill
-    # 8192 bytes exactly: the second group's first frame starts on the tile edge
-    edge = [[(A0, [("P", 9, ((1, 2), (4, 5))), ("P", 8, ((1, 2), (4, 5), (7, 8)))] +
-              [("F", 20 * k, 20 * k + 3) for k in range(143)])],
-            [(U.ACTORS[1], [("F", 1, 5), ("P", 2, ((0, 0),))])]]
     res = run_sessions([edge], 10, 10, mem)
     assert res["frame_off"][res["grp_frame_off"][1]] == 8192
     run_sessions([big, many, edge, big], 10, 10, mem)
@@ -140,14 +131,7 @@ def test_tile_edges(mem):
 
 @pytest.mark.parametrize("mem", MEMS)
 def test_quirks(mem):
-    sessions = [
-        [[(A0, [("F", 1, 21)])]],                                   # (e - s) % chunk == 0: a trailing one-version chunk
-        [[(A0, [("F", 9, 3), ("F", 4, 4)])], [(A0, [("F", 7, 2)])]],  # s > e: no item; a server left without items
-        [[(A0, [("P", 5, ()), ("P", 6, ((3, 3),))])]],               # an empty seq list: no frame
-        [[(A0, [("P", 5, ((0, 4), (5, 9)))])]],                       # adjacent seqs merge
-        [[(A0, [("F", 1, 30), ("P", 2, ((0, 9),))])], [(A0, [("F", 5, 25), ("P", 2, ((2, 3), (9, 9)))])],
-         [(U.ACTORS[2], [("F", 1, 3)])]],                            # a server all of whose items are deduped away
-    ]
+    sessions = U.quirk_sessions()
     res = run_sessions(sessions, 10, 10, mem)
     arr, groups = U.flatten(sessions, SITE_OF)
     gfo = res["grp_frame_off"]
@@ -228,7 +212,7 @@ BAD = [(_bad_kind, 10, 10, -1), (_bad_site, 10, 10, -1), (_need_off_not_monotone
        (_too_many_items, 1, 10, -6)]
 
 
-def _raw(arr, chunk, drain, pass_, o, mem):
+def _raw(arr, chunk, drain, pass_, o, mem, eng=None):
     keep = to_dev(arr) if mem == "device" else arr
     ptr = (lambda a: a.data_ptr() if a.numel() else None) if mem == "device" else (lambda a: a.ctypes.data if a.size else None)
     r = L.RequestIn()
@@ -239,7 +223,7 @@ def _raw(arr, chunk, drain, pass_, o, mem):
     if mem == "device":
         import torch
         torch.cuda.synchronize()
-    return L.lib().corro_plan_requests(engine()._h, C.byref(r), L.CORRO_MEM_DEVICE if mem == "device" else 0, C.byref(o), pass_)
+    return L.lib().corro_plan_requests((eng or engine())._h, C.byref(r), L.CORRO_MEM_DEVICE if mem == "device" else 0, C.byref(o), pass_)
 
 
 @pytest.mark.parametrize("mem", MEMS)
