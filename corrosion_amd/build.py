@@ -12,7 +12,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libcorro_hip.so")
 SOURCES = ["engine.hip", "sync_needs.hip", "partition.hip", "prims.hip", "extract.hip", "wire.hip", "wire_encode.hip", "req_plan.hip", "req_decode.hip", "state_decode.hip", "state_encode.hip", "match.hip", "need_tails.hip", "answer_assemble.hip", "buffered_serve.hip", "booked.cpp", "agent.cpp",
            "pkeys.hip", "gaps.hip", "affinity.hip", "agent_dev.hip", "bufpool.hip", "values_compact.hip"]
-HEADERS = ["internal.h", "merge_kernels.h", "ovf_kernels.h", "ranges.h", "booked.h", "rowhash.h", "rowstore.h", "agent_dev.h", "scratch.h", "scratch_core.h"]
+HEADERS = ["internal.h", "merge_kernels.h", "ovf_kernels.h", "ranges.h", "booked.h", "rowhash.h", "rowstore.h", "agent_dev.h", "scratch.h", "scratch_core.h", "search.h"]
 ARCH = "gfx950"
 
 

@@ -37,6 +37,7 @@
 
 #include "internal.h"
 #include "scratch.h"
+#include "search.h"
 
 namespace corro {
 int prim_inclusive_sum_u64(void *temp, size_t *temp_bytes, const uint64_t *in, uint64_t *out, uint64_t n, hipStream_t s);
@@ -62,28 +63,6 @@ struct AsDev {
     uint64_t *need_ans_off, *frame_ans_off;        // nneeds + 1, nframes + 1
     uint8_t *frame_host;                           // nframes
 };
-
-// first index in [0, len) whose element is > v (len if none): memory-safe whatever the array holds
-__device__ inline uint64_t ub64(const uint64_t *a, uint64_t len, uint64_t v) {
-    uint64_t lo = 0, hi = len;
-    while (lo < hi) {
-        const uint64_t mid = lo + (hi - lo) / 2;
-        if (a[mid] <= v) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
-// first index in [0, len) whose element is >= v (len if none)
-__device__ inline uint64_t lb64(const uint64_t *a, uint64_t len, uint64_t v) {
-    uint64_t lo = 0, hi = len;
-    while (lo < hi) {
-        const uint64_t mid = lo + (hi - lo) / 2;
-        if (a[mid] < v) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
 
 template <int P> __global__ void k_as_check(AsDev d) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;

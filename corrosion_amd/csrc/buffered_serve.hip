@@ -31,6 +31,7 @@
 #include "agent_dev.h"
 #include "internal.h"
 #include "scratch.h"
+#include "search.h"
 
 namespace corro {
 int prim_inclusive_sum_u64(void *temp, size_t *temp_bytes, const uint64_t *in, uint64_t *out, uint64_t n, hipStream_t s);
@@ -48,28 +49,6 @@ struct BsDev {
     uint64_t *pdst, *psrc;                 // per piece: its first output row, its first pool row
     corro_bufspans_out out;
 };
-
-// first index in [0, len) whose element is > v (len if none): memory-safe whatever the array holds
-__device__ inline uint64_t ub64(const uint64_t *a, uint64_t len, uint64_t v) {
-    uint64_t lo = 0, hi = len;
-    while (lo < hi) {
-        const uint64_t mid = lo + (hi - lo) / 2;
-        if (a[mid] <= v) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
-// first index in [0, len) whose element is >= v (len if none)
-__device__ inline uint64_t lb64(const uint64_t *a, uint64_t len, uint64_t v) {
-    uint64_t lo = 0, hi = len;
-    while (lo < hi) {
-        const uint64_t mid = lo + (hi - lo) / 2;
-        if (a[mid] < v) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
 
 // element i + 1 of a CSR's values belongs to element i's slice unless the next slice starts there
 // (off holds n + 1 offsets)

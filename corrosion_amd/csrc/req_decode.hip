@@ -29,6 +29,7 @@
 
 #include "internal.h"
 #include "scratch.h"
+#include "search.h"
 
 namespace corro {
 int prim_inclusive_sum_u64(void *temp, size_t *temp_bytes, const uint64_t *in, uint64_t *out, uint64_t n, hipStream_t s);
@@ -59,17 +60,6 @@ struct RdDev {
     uint64_t *o_pair, *o_need, *o_seq, *o_ent;
     corro_reqdec_out out;                  // fill walk
 };
-
-// first index in [0, len) whose element is > v (len if none): memory-safe whatever the array holds
-__device__ inline uint64_t ub64(const uint64_t *a, uint64_t len, uint64_t v) {
-    uint64_t lo = 0, hi = len;
-    while (lo < hi) {
-        const uint64_t mid = lo + (hi - lo) / 2;
-        if (a[mid] <= v) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
 
 __global__ void k_rd_check(RdDev d) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;

@@ -42,6 +42,7 @@
 
 #include "internal.h"
 #include "scratch.h"
+#include "search.h"
 
 namespace corro {
 int ovf_sort_pairs(void *temp, size_t *temp_bytes, const uint64_t *ki, uint64_t *ko, const uint32_t *vi,
@@ -102,17 +103,6 @@ struct ReqDev {
     uint64_t *grp_frame_off, *frame_off, *frame_entry;
     uint32_t *frame_round, *frame_needs;
 };
-
-// first index in [0, len) whose element is > v (len if none): memory-safe whatever the array holds
-__device__ inline uint64_t ub64(const uint64_t *a, uint64_t len, uint64_t v) {
-    uint64_t lo = 0, hi = len;
-    while (lo < hi) {
-        const uint64_t mid = lo + (hi - lo) / 2;
-        if (a[mid] <= v) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
 
 __device__ inline void raise_max(unsigned long long *p, uint64_t v) {
     if (v > *(volatile unsigned long long *)p) atomicMax(p, (unsigned long long)v);
@@ -363,8 +353,6 @@ __global__ void k_req_ftab(ReqDev d) {
     d.frame_needs[f] = gs_kind(d, d.o_gs[o]) ? 1u : d.poff[o + 1] - d.poff[o];
     d.f_o[f] = o;
 }
-
-__device__ inline uint32_t half(uint64_t v, uint32_t hi) { return (uint32_t)(hi ? v >> 32 : v); }
 
 // word k of frame f (frame bytes [fo, fe))
 __device__ inline uint32_t frame_word(const ReqDev &d, uint64_t f, uint32_t k, uint64_t fo, uint64_t fe) {

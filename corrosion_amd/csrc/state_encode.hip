@@ -36,6 +36,7 @@
 
 #include "internal.h"
 #include "scratch.h"
+#include "search.h"
 
 namespace corro {
 int prim_inclusive_sum_u64(void *temp, size_t *temp_bytes, const uint64_t *in, uint64_t *out, uint64_t n, hipStream_t s);
@@ -68,17 +69,6 @@ struct SeDev {
     uint64_t W, NB;                        // write pass: total words and bytes
 };
 
-// first index in [0, len) whose element is > v (len if none): memory-safe whatever the array holds
-__device__ inline uint64_t ub64(const uint64_t *a, uint64_t len, uint64_t v) {
-    uint64_t lo = 0, hi = len;
-    while (lo < hi) {
-        const uint64_t mid = lo + (hi - lo) / 2;
-        if (a[mid] <= v) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
 // the element of the exclusive scan `off` over [lo, hi) that holds `target`: off[x] <= target < off[x + 1]
 // (elements of size 0 share their offset with their successor and are never returned for a target inside
 // [off[lo], off[hi])); clamped into [lo, hi - 1] whatever the arrays hold
@@ -86,11 +76,6 @@ __device__ inline uint64_t holder(const uint64_t *off, uint64_t lo, uint64_t hi,
     const uint64_t k = ub64(off + lo, hi - lo + 1, target);
     return lo + std::min<uint64_t>(k ? k - 1 : 0, hi - lo - 1);
 }
-
-__device__ inline uint32_t ld32(const uint8_t *p) {
-    return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
-}
-__device__ inline uint32_t half(uint64_t v, uint64_t hi) { return (uint32_t)(hi ? v >> 32 : v); }
 
 // s does not clear e_prev by at least one missing value: unsorted, overlapping or touching
 __device__ inline bool not_clear(uint64_t e_prev, uint64_t s) { return !(s > e_prev && s - e_prev >= 2); }

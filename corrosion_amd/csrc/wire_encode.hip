@@ -31,6 +31,7 @@
 
 #include "internal.h"
 #include "scratch.h"
+#include "search.h"
 
 namespace corro {
 int prim_inclusive_scan_u32_u64(void *temp, size_t *temp_bytes, const uint32_t *in, uint64_t *out, uint64_t n,
@@ -272,17 +273,8 @@ __global__ void __launch_bounds__(64) k_enc_write(EncDev d) {
     const uint32_t tl = (uint32_t)(T1 - T0);
     const uint32_t HDR = hdr_bytes(d.payload), TR = tail_bytes(d.payload);
     // the frame holding the tile's first byte (frame offsets strictly increase; frame_off[0] = 0)
-    uint64_t f;
-    {
-        uint64_t lo = 0, hi = d.nframes;
-        while (lo < hi) {
-            const uint64_t mid = lo + (hi - lo) / 2;
-            if (d.frame_off[mid] <= T0) lo = mid + 1;
-            else hi = mid;
-        }
-        f = lo ? lo - 1 : 0;
-    }
-    for (; f < d.nframes; f++) {
+    const uint64_t ub = ub64(d.frame_off, d.nframes, T0);
+    for (uint64_t f = ub ? ub - 1 : 0; f < d.nframes; f++) {
         const uint64_t fo = d.frame_off[f];
         if (fo >= T1) break;
         const uint64_t fe = d.frame_off[f + 1];

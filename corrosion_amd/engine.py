@@ -11,6 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
+from ._twopass import Mem, _int_dtype_ok, _is_torch, two_pass
 
 BATCH_FIELDS = {"pk": np.uint64, "table_cid": np.uint32, "col_version": np.int64,
                 "db_version": np.int64, "cl": np.uint32, "seq": np.uint32, "site": np.uint32,
@@ -26,17 +27,24 @@ ROW_FIELDS = {"pk": np.uint64, "table_cid": np.uint32, "col_version": np.int64,
               "val_len": np.uint8}
 
 
-def _is_torch(x):
-    return type(x).__module__.startswith("torch")
-
-
-def _int_dtype_ok(t, dt):
-    """A device field's tensor must be an integer type of the field's width (signed or unsigned: the
-    C ABI reads the bits); a float, bool or wider/narrower tensor is rejected, not reinterpreted."""
-    import torch
-    ok = {8: (torch.int64, getattr(torch, "uint64", None)), 4: (torch.int32, getattr(torch, "uint32", None)),
-          2: (torch.int16, getattr(torch, "uint16", None)), 1: (torch.uint8, torch.int8)}
-    return t.dtype in ok.get(np.dtype(dt).itemsize, ())
+# corro_encode_in's span arrays: what need_spans and buffered_spans return and encode_changesets takes
+SPAN_FIELDS = (("site", np.uint32), ("version", np.int64), ("last_seq", np.uint64), ("ts", np.uint64),
+               ("seq_start", np.uint64), ("seq_end", np.uint64), ("row_off", np.uint64), ("row_count", np.uint64))
+SPAN_KEYS = tuple(k for k, _dt in SPAN_FIELDS)
+# pass-1 output tables (see _twopass): name, dtype, the total that sizes it, and where needed mul, extra
+_SPANS_OUT = tuple((k, dt, "nspans") for k, dt in SPAN_FIELDS)
+_ENC_OUT = (("buf", np.uint8, "nbytes"), ("frame_off", np.uint64, "nframes", 1, 1),
+            ("frame_seq_start", np.uint64, "nframes"), ("frame_seq_end", np.uint64, "nframes"),
+            ("frame_row_off", np.uint64, "nframes"), ("frame_rows", np.uint32, "nframes"))
+_REQDEC_OUT = (("pair_actor", np.uint8, "npairs", 16, 0), ("pair_site", np.uint32, "npairs"),
+               ("pair_need_off", np.uint64, "npairs", 1, 1), ("kind", np.uint8, "nneeds"),
+               ("start", np.uint64, "nneeds"), ("end", np.uint64, "nneeds"), ("sr_off", np.uint64, "nneeds"),
+               ("sr_n", np.uint64, "nneeds"), ("s_start", np.uint64, "nseqs"), ("s_end", np.uint64, "nseqs"),
+               ("need_site", np.uint32, "nneeds"), ("need_keep", np.uint8, "nneeds"),
+               ("need_ent_off", np.uint64, "nneeds", 1, 1), ("ent_site", np.uint32, "nents"),
+               ("ent_start", np.uint64, "nents"), ("ent_end", np.uint64, "nents"),
+               ("ent_seq_start", np.uint32, "nents"), ("ent_seq_end", np.uint32, "nents"),
+               ("ent_need", np.uint64, "nents"))
 
 
 class MergeEngine:
@@ -721,10 +729,6 @@ class MergeEngine:
         (uint8, the frames in span order then chunk order), "frame_off" (nframes + 1),
         "span_frame_off" (n + 1) and per frame "frame_seq_start", "frame_seq_end", "frame_row_off",
         "frame_rows", in the same memory, plus "nframes" / "nbytes"."""
-        lib = L.lib()
-        span_fields = (("site", np.uint32), ("version", np.int64), ("last_seq", np.uint64), ("ts", np.uint64),
-                       ("seq_start", np.uint64), ("seq_end", np.uint64), ("row_off", np.uint64),
-                       ("row_count", np.uint64))
         row_fields = [(k, dt) for k, dt in ROW_FIELDS.items() if k != "ts"]
         on_dev = _is_torch(spans["site"])
         n, R = int(spans["site"].shape[0]), int(rows["pk"].shape[0])
@@ -732,7 +736,7 @@ class MergeEngine:
         s.n, s.nrows = n, R
         s.max_buf_size, s.payload, s.cluster_id = int(max_buf_size), int(payload), int(cluster_id)
         keep = []
-        for src, dst, fields, cnt in ((spans, s, span_fields, n), (rows, s.rows, row_fields, R)):
+        for src, dst, fields, cnt in ((spans, s, SPAN_FIELDS, n), (rows, s.rows, row_fields, R)):
             for k, dt in fields:
                 a = src[k]
                 if on_dev:
@@ -746,45 +750,11 @@ class MergeEngine:
                         raise ValueError(f"field {k} must hold {cnt} entries")
                     keep.append(a)
                     setattr(dst, k, a.ctypes.data if cnt else None)
-        if on_dev:
-            import torch
-            dev = spans["site"].device
-            tdt = {np.uint64: torch.int64, np.uint32: torch.int32, np.uint8: torch.uint8}
-
-            def alloc(cnt, dt):
-                return torch.empty(max(cnt, 1), dtype=tdt[dt], device=dev)
-
-            def ptr(a):
-                return a.data_ptr()
-            sync = torch.cuda.current_stream().synchronize
-        else:
-            def alloc(cnt, dt):
-                return np.zeros(max(cnt, 1), dt)
-
-            def ptr(a):
-                return a.ctypes.data
-
-            def sync():
-                pass
-        mem = L.CORRO_MEM_DEVICE if on_dev else L.CORRO_MEM_HOST
-        o = L.Encoded()
-        sfo = alloc(n + 1, np.uint64)
-        o.span_frame_off = ptr(sfo)
-        sync()
-        L.check(lib.corro_encode_changesets(self._h, C.byref(s), mem, C.byref(o), 0))
-        F, NB = int(o.nframes), int(o.nbytes)
+        mem = Mem.of(spans["site"])
+        res = two_pass(L.lib().corro_encode_changesets, (self._h, C.byref(s), mem.const), mem, L.Encoded(),
+                       (("span_frame_off", np.uint64, n + 1),), ("nframes", "nbytes"), _ENC_OUT)
         if n == 0:
-            sfo[:1] = 0
-        res = {"buf": alloc(NB, np.uint8), "frame_off": alloc(F + 1, np.uint64),
-               "frame_seq_start": alloc(F, np.uint64), "frame_seq_end": alloc(F, np.uint64),
-               "frame_row_off": alloc(F, np.uint64), "frame_rows": alloc(F, np.uint32)}
-        for k, a in res.items():
-            setattr(o, k, ptr(a))
-        sync()
-        L.check(lib.corro_encode_changesets(self._h, C.byref(s), mem, C.byref(o), 1))
-        res = {k: a[:(NB if k == "buf" else F + 1 if k == "frame_off" else F)] for k, a in res.items()}
-        res["span_frame_off"] = sfo[:n + 1]
-        res["nframes"], res["nbytes"] = F, NB
+            res["span_frame_off"][:1] = 0
         return res
 
     # ---- sync request decode (the server's half of plan_requests) ---------------------------
@@ -826,17 +796,6 @@ class MergeEngine:
             return a, None
         return a, (a.data_ptr() if on_dev else a.ctypes.data)
 
-    _REQDEC_OUT = (("pair_actor", np.uint8, "npairs", 16, 0), ("pair_site", np.uint32, "npairs", 1, 0),
-                   ("pair_need_off", np.uint64, "npairs", 1, 1), ("kind", np.uint8, "nneeds", 1, 0),
-                   ("start", np.uint64, "nneeds", 1, 0), ("end", np.uint64, "nneeds", 1, 0),
-                   ("sr_off", np.uint64, "nneeds", 1, 0), ("sr_n", np.uint64, "nneeds", 1, 0),
-                   ("s_start", np.uint64, "nseqs", 1, 0), ("s_end", np.uint64, "nseqs", 1, 0),
-                   ("need_site", np.uint32, "nneeds", 1, 0), ("need_keep", np.uint8, "nneeds", 1, 0),
-                   ("need_ent_off", np.uint64, "nneeds", 1, 1), ("ent_site", np.uint32, "nents", 1, 0),
-                   ("ent_start", np.uint64, "nents", 1, 0), ("ent_end", np.uint64, "nents", 1, 0),
-                   ("ent_seq_start", np.uint32, "nents", 1, 0), ("ent_seq_end", np.uint32, "nents", 1, 0),
-                   ("ent_need", np.uint64, "nents", 1, 0))
-
     def decode_requests(self, buf, frame_off, book=None):
         """SyncMessageV1::Request frames -> decoded, screened needs and their extraction entries on the
         GPU (corro_decode_requests). buf: the frames back to back (bytes / numpy uint8, or a CUDA uint8
@@ -849,49 +808,31 @@ class MergeEngine:
         entries "ent_site", "ent_start", "ent_end", "ent_seq_start", "ent_seq_end", "ent_need", and
         the totals "nframes", "npairs", "nneeds", "nseqs", "nents". With device input only the totals
         reach the host."""
-        lib = L.lib()
-        on_dev = _is_torch(buf)
-        if not on_dev and not isinstance(buf, np.ndarray):
+        mem = Mem.of(buf)
+        if not mem.on_dev and not isinstance(buf, np.ndarray):
             buf = np.frombuffer(bytes(buf), np.uint8)
-        keep = []
         r = L.ReqDecIn()
-        b, r.buf = self._in_field(buf, np.uint8, on_dev, "buf")
-        fo, r.frame_off = self._in_field(frame_off, np.uint64, on_dev, "frame_off")
-        keep += [b, fo]
-        r.len = int(b.numel() if on_dev else b.size)
-        nfo = int(fo.numel() if on_dev else fo.size)
-        if nfo < 1:
+        b, r.buf = mem.field(buf, np.uint8, "buf")
+        fo, r.frame_off = mem.field(frame_off, np.uint64, "frame_off")
+        keep = [b, fo]
+        r.len = mem.count(b)
+        if mem.count(fo) < 1:
             raise ValueError("frame_off holds nframes + 1 offsets")
-        F = nfo - 1
+        F = mem.count(fo) - 1
         r.nframes = F
         if book is not None:
-            S = int(book["known"].numel() if on_dev else np.asarray(book["known"]).size)
+            S = mem.count(book["known"]) if mem.on_dev else np.asarray(book["known"]).size
             r.book_nsites = S
             for k, dst, dt, cnt in (("known", "book_known", np.uint8, S), ("max", "book_max", np.int64, S),
                                     ("gap_off", "gap_off", np.uint64, S + 1), ("gap_start", "gap_start", np.uint64, None),
                                     ("gap_end", "gap_end", np.uint64, None)):
-                a, p = self._in_field(book[k], dt, on_dev, "book." + k, cnt)
+                a, p = mem.field(book[k], dt, "book." + k, cnt)
                 keep.append(a)
                 setattr(r, dst, p)
-            r.book_ngaps = int(keep[-1].numel() if on_dev else keep[-1].size)
-        alloc, ptr, sync = self._two_pass_io(on_dev, buf.device if on_dev else None)
-        mem = L.CORRO_MEM_DEVICE if on_dev else L.CORRO_MEM_HOST
-        o = L.ReqDecOut()
-        st, fpo = alloc(F, np.int32), alloc(F + 1, np.uint64)
-        o.frame_status, o.frame_pair_off = ptr(st), ptr(fpo)
-        sync()
-        L.check(lib.corro_decode_requests(self._h, C.byref(r), mem, C.byref(o), 0))
-        tot = {k: int(getattr(o, k)) for k in ("npairs", "nneeds", "nseqs", "nents")}
-        res = {}
-        for k, dt, size, mul, extra in self._REQDEC_OUT:
-            res[k] = alloc(tot[size] * mul + extra, dt)
-            setattr(o, k, ptr(res[k]))
-        sync()
-        L.check(lib.corro_decode_requests(self._h, C.byref(r), mem, C.byref(o), 1))
-        for k, _dt, size, mul, extra in self._REQDEC_OUT:
-            res[k] = res[k][:tot[size] * mul + extra]
-        res["frame_status"], res["frame_pair_off"] = st[:F], fpo[:F + 1]
-        res.update(tot)
+            r.book_ngaps = mem.count(keep[-1])
+        res = two_pass(L.lib().corro_decode_requests, (self._h, C.byref(r), mem.const), mem, L.ReqDecOut(),
+                       (("frame_status", np.int32, F), ("frame_pair_off", np.uint64, F + 1)),
+                       ("npairs", "nneeds", "nseqs", "nents"), _REQDEC_OUT)
         res["nframes"] = F
         return res
 
@@ -901,40 +842,18 @@ class MergeEngine:
         arrays (same memory). Returns the spans dict encode_changesets takes ("site", "version",
         "last_seq", "ts", "seq_start", "seq_end", "row_off", "row_count") plus "need_span_off"
         (nneeds + 1), "in_state" (per need: a kept Partial's version is in the state) and "nspans"."""
-        lib = L.lib()
-        on_dev = _is_torch(dec["kind"])
+        mem = Mem.of(dec["kind"])
         T, Q, E = int(dec["nneeds"]), int(dec["nseqs"]), int(dec["nents"])
         G = int(ext["version"].shape[0])
         s = L.SpansIn()
         s.nneeds, s.nseqs, s.nents, s.ngroups = T, Q, E, G
-        keep = []
-        for src, k, dt, cnt in ((dec, "kind", np.uint8, T), (dec, "sr_off", np.uint64, T), (dec, "sr_n", np.uint64, T),
-                                (dec, "s_start", np.uint64, Q), (dec, "s_end", np.uint64, Q),
-                                (dec, "need_keep", np.uint8, T), (dec, "need_ent_off", np.uint64, T + 1),
-                                (dec, "need_site", np.uint32, T), (ext, "grp_off", np.uint64, E + 1),
-                                (ext, "version", np.int64, G), (ext, "last_seq", np.uint64, G), (ext, "ts", np.uint64, G),
-                                (ext, "grp_row_off", np.uint64, G), (ext, "grp_rows", np.uint64, G)):
-            a, p = self._in_field(src[k], dt, on_dev, k, cnt)
-            keep.append(a)
-            setattr(s, k, p)
-        alloc, ptr, sync = self._two_pass_io(on_dev, dec["kind"].device if on_dev else None)
-        mem = L.CORRO_MEM_DEVICE if on_dev else L.CORRO_MEM_HOST
-        o = L.SpansOut()
-        nso, ins = alloc(T + 1, np.uint64), alloc(T, np.uint8)
-        o.need_span_off, o.in_state = ptr(nso), ptr(ins)
-        sync()
-        L.check(lib.corro_need_spans(self._h, C.byref(s), mem, C.byref(o), 0))
-        N = int(o.nspans)
-        res = {}
-        for k, dt in (("site", np.uint32), ("version", np.int64), ("last_seq", np.uint64), ("ts", np.uint64),
-                      ("seq_start", np.uint64), ("seq_end", np.uint64), ("row_off", np.uint64), ("row_count", np.uint64)):
-            res[k] = alloc(N, dt)
-            setattr(o, k, ptr(res[k]))
-        sync()
-        L.check(lib.corro_need_spans(self._h, C.byref(s), mem, C.byref(o), 1))
-        res = {k: a[:N] for k, a in res.items()}
-        res["need_span_off"], res["in_state"], res["nspans"] = nso[:T + 1], ins[:T], N
-        return res
+        keep = mem.fill(s, dec, (("kind", np.uint8, T), ("sr_off", np.uint64, T), ("sr_n", np.uint64, T),
+                                 ("s_start", np.uint64, Q), ("s_end", np.uint64, Q), ("need_keep", np.uint8, T),
+                                 ("need_ent_off", np.uint64, T + 1), ("need_site", np.uint32, T)))
+        keep += mem.fill(s, ext, (("grp_off", np.uint64, E + 1), ("version", np.int64, G), ("last_seq", np.uint64, G),
+                                  ("ts", np.uint64, G), ("grp_row_off", np.uint64, G), ("grp_rows", np.uint64, G)))
+        return two_pass(L.lib().corro_need_spans, (self._h, C.byref(s), mem.const), mem, L.SpansOut(),
+                        (("need_span_off", np.uint64, T + 1), ("in_state", np.uint8, T)), ("nspans",), _SPANS_OUT)
 
     def need_tails(self, dec, ext, sp, bufbook, payload=0, cluster_id=0):
         """The Changeset::Empty frames that end the answers to the decoded needs, on the GPU
@@ -945,8 +864,7 @@ class MergeEngine:
         "nranges", "need_tail_off" (nneeds + 1), "need_host" (per need: 1 = it touches a buffered version
         and the host answers its tail), "range_start", "range_end", "buf" (one frame per range: 49 bytes
         for payload 0, 55 for the uni payload 1) and "frame_off"."""
-        lib = L.lib()
-        on_dev = _is_torch(dec["kind"])
+        mem = Mem.of(dec["kind"])
         T, E = int(dec["nneeds"]), int(dec["nents"])
         G = int(ext["version"].shape[0])
         S = len(bufbook["gap_off"]) - 1
@@ -955,37 +873,56 @@ class MergeEngine:
         r = L.TailsIn()
         r.nneeds, r.nents, r.ngroups, r.book_nsites = T, E, G, S
         r.payload, r.cluster_id = payload, cluster_id
-        keep = []
-        for src, k, dt, cnt in ((dec, "kind", np.uint8, T), (dec, "start", np.uint64, T), (dec, "end", np.uint64, T),
-                                (dec, "need_keep", np.uint8, T), (dec, "need_site", np.uint32, T),
-                                (dec, "need_ent_off", np.uint64, T + 1), (sp, "in_state", np.uint8, T),
-                                (ext, "grp_off", np.uint64, E + 1), (ext, "version", np.int64, G),
-                                (bufbook, "gap_off", np.uint64, S + 1), (bufbook, "gap_start", np.uint64, None),
-                                (bufbook, "gap_end", np.uint64, None), (bufbook, "buf_off", np.uint64, S + 1),
-                                (bufbook, "buf_version", np.uint64, None)):
-            a, p = self._in_field(src[k], dt, on_dev, k, cnt)
-            keep.append(a)
-            setattr(r, k, p)
+        keep = mem.fill(r, dec, (("kind", np.uint8, T), ("start", np.uint64, T), ("end", np.uint64, T),
+                                 ("need_keep", np.uint8, T), ("need_site", np.uint32, T),
+                                 ("need_ent_off", np.uint64, T + 1)))
+        keep += mem.fill(r, sp, (("in_state", np.uint8, T),))
+        keep += mem.fill(r, ext, (("grp_off", np.uint64, E + 1), ("version", np.int64, G)))
+        keep += mem.fill(r, bufbook, (("gap_off", np.uint64, S + 1), ("gap_start", np.uint64, None),
+                                      ("gap_end", np.uint64, None), ("buf_off", np.uint64, S + 1),
+                                      ("buf_version", np.uint64, None)))
         r.book_ngaps, r.book_nbuf = int(keep[-3].shape[0]), int(keep[-1].shape[0])
         if int(keep[-4].shape[0]) != r.book_ngaps:
             raise ValueError("gap_start and gap_end must hold the same number of gaps")
-        alloc, ptr, sync = self._two_pass_io(on_dev, dec["kind"].device if on_dev else None)
-        mem = L.CORRO_MEM_DEVICE if on_dev else L.CORRO_MEM_HOST
-        o = L.TailsOut()
-        nto, nh = alloc(T + 1, np.uint64), alloc(T, np.uint8)
-        o.need_tail_off, o.need_host = ptr(nto), ptr(nh)
-        sync()
-        L.check(lib.corro_need_tails(self._h, C.byref(r), mem, C.byref(o), 0))
-        N, NB = int(o.nranges), int(o.nbytes)
-        res = {"range_start": alloc(N, np.uint64), "range_end": alloc(N, np.uint64), "buf": alloc(NB, np.uint8),
-               "frame_off": alloc(N + 1, np.uint64)}
-        for k, a in res.items():
-            setattr(o, k, ptr(a))
-        sync()
-        L.check(lib.corro_need_tails(self._h, C.byref(r), mem, C.byref(o), 1))
-        res = {k: a[:(NB if k == "buf" else N + 1 if k == "frame_off" else N)] for k, a in res.items()}
-        res["need_tail_off"], res["need_host"], res["nranges"] = nto[:T + 1], nh[:T], N
+        res = two_pass(L.lib().corro_need_tails, (self._h, C.byref(r), mem.const), mem, L.TailsOut(),
+                       (("need_tail_off", np.uint64, T + 1), ("need_host", np.uint8, T)), ("nranges", "nbytes"),
+                       (("range_start", np.uint64, "nranges"), ("range_end", np.uint64, "nranges"),
+                        ("buf", np.uint8, "nbytes"), ("frame_off", np.uint64, "nranges", 1, 1)))
+        del res["nbytes"]
         return res
+
+    def _assemble(self, dec, sp, enc, tl, payload, bsp=None, benc=None):
+        """assemble_answers, or with bsp assemble_answers_buffered: the same base input and output."""
+        mem = Mem.of(dec["frame_pair_off"])
+        F, NP, T = int(dec["nframes"]), int(dec["npairs"]), int(dec["nneeds"])
+        NS, NR = int(sp["nspans"]), int(tl["nranges"])
+        rb = L.AssembleIn() if bsp is None else L.AssembleBufferedIn()
+        r = rb if bsp is None else rb.base
+        r.nframes, r.npairs, r.nneeds, r.nspans, r.nranges, r.payload = F, NP, T, NS, NR, int(payload)
+        r.enc_nframes, r.enc_nbytes = (int(enc["nframes"]), int(enc["nbytes"])) if NS else (0, 0)
+        r.tail_nbytes = int(tl["buf"].shape[0])
+        keep = mem.fill(r, dec, (("frame_pair_off", np.uint64, F + 1), ("pair_need_off", np.uint64, NP + 1),
+                                 ("need_keep", np.uint8, T)))
+        keep += mem.fill(r, sp, (("need_span_off", np.uint64, T + 1),))
+        keep += mem.fill(r, tl, (("need_tail_off", np.uint64, T + 1), ("need_host", np.uint8, T),
+                                 ("buf", np.uint8, None, "tail_buf")))
+        if NS:
+            keep += mem.fill(r, enc, (("span_frame_off", np.uint64, NS + 1),
+                                      ("frame_off", np.uint64, r.enc_nframes + 1, "enc_frame_off"),
+                                      ("buf", np.uint8, r.enc_nbytes, "enc_buf")))
+        fn = L.lib().corro_assemble_answers
+        if bsp is not None:
+            fn = L.lib().corro_assemble_answers_buffered
+            BS = rb.nbspans = int(bsp["nspans"])
+            rb.benc_nframes, rb.benc_nbytes = (int(benc["nframes"]), int(benc["nbytes"])) if BS else (0, 0)
+            keep += mem.fill(rb, bsp, (("need_bspan_off", np.uint64, T + 1),))
+            if BS:
+                keep += mem.fill(rb, benc, (("span_frame_off", np.uint64, BS + 1, "bspan_frame_off"),
+                                            ("frame_off", np.uint64, rb.benc_nframes + 1, "benc_frame_off"),
+                                            ("buf", np.uint8, rb.benc_nbytes, "benc_buf")))
+        return two_pass(fn, (self._h, C.byref(rb), mem.const), mem, L.Assembled(),
+                        (("need_ans_off", np.uint64, T + 1), ("frame_ans_off", np.uint64, F + 1),
+                         ("frame_host", np.uint8, F)), ("nbytes",), (("buf", np.uint8, "nbytes"),))
 
     def assemble_answers(self, dec, sp, enc, tl, payload=0):
         """The per-frame answers to the decoded request frames in one buffer, on the GPU
@@ -996,42 +933,7 @@ class MergeEngine:
         need_tails. Returns, in that memory, "buf" (uint8), "need_ans_off" (nneeds + 1), "frame_ans_off" (nframes + 1: the answer of frame f
         is buf[off[f]:off[f + 1]]) and "frame_host" (per frame: 1 = a kept need of it has need_host,
         and the host splices that need's bookie messages in at need_ans_off[t + 1]), plus "nbytes"."""
-        lib = L.lib()
-        on_dev = _is_torch(dec["frame_pair_off"])
-        F, NP, T = int(dec["nframes"]), int(dec["npairs"]), int(dec["nneeds"])
-        NS, NR = int(sp["nspans"]), int(tl["nranges"])
-        r = L.AssembleIn()
-        r.nframes, r.npairs, r.nneeds, r.nspans, r.nranges, r.payload = F, NP, T, NS, NR, int(payload)
-        r.enc_nframes, r.enc_nbytes = (int(enc["nframes"]), int(enc["nbytes"])) if NS else (0, 0)
-        r.tail_nbytes = int(tl["buf"].shape[0])
-        keep = []
-        fields = [(dec, "frame_pair_off", "frame_pair_off", np.uint64, F + 1),
-                  (dec, "pair_need_off", "pair_need_off", np.uint64, NP + 1), (dec, "need_keep", "need_keep", np.uint8, T),
-                  (sp, "need_span_off", "need_span_off", np.uint64, T + 1),
-                  (tl, "need_tail_off", "need_tail_off", np.uint64, T + 1), (tl, "need_host", "need_host", np.uint8, T),
-                  (tl, "buf", "tail_buf", np.uint8, None)]
-        if NS:
-            fields += [(enc, "span_frame_off", "span_frame_off", np.uint64, NS + 1),
-                       (enc, "frame_off", "enc_frame_off", np.uint64, r.enc_nframes + 1),
-                       (enc, "buf", "enc_buf", np.uint8, r.enc_nbytes)]
-        for src, k, dst, dt, cnt in fields:
-            a, p = self._in_field(src[k], dt, on_dev, k, cnt)
-            keep.append(a)
-            setattr(r, dst, p)
-        alloc, ptr, sync = self._two_pass_io(on_dev, dec["frame_pair_off"].device if on_dev else None)
-        mem = L.CORRO_MEM_DEVICE if on_dev else L.CORRO_MEM_HOST
-        o = L.Assembled()
-        nao, fao, fh = alloc(T + 1, np.uint64), alloc(F + 1, np.uint64), alloc(F, np.uint8)
-        o.need_ans_off, o.frame_ans_off, o.frame_host = ptr(nao), ptr(fao), ptr(fh)
-        sync()
-        L.check(lib.corro_assemble_answers(self._h, C.byref(r), mem, C.byref(o), 0))
-        NB = int(o.nbytes)
-        buf = alloc(NB, np.uint8)
-        o.buf = ptr(buf)
-        sync()
-        L.check(lib.corro_assemble_answers(self._h, C.byref(r), mem, C.byref(o), 1))
-        return {"buf": buf[:NB], "need_ans_off": nao[:T + 1], "frame_ans_off": fao[:F + 1], "frame_host": fh[:F],
-                "nbytes": NB}
+        return self._assemble(dec, sp, enc, tl, payload)
 
     _BUFIDX_IN = (("ver_off", "ver_off", np.uint64), ("version", "idx_version", np.uint64),
                   ("last_seq", "idx_last_seq", np.int64), ("ts", "idx_ts", np.uint64), ("on_device", "on_device", np.uint8),
@@ -1046,10 +948,9 @@ class MergeEngine:
         "need_host"); idx: that index's "dev" arrays. CUDA tensors only: the pool rows stay on the
         device. Returns the spans dict encode_changesets takes, "need_bspan_off" (nneeds + 1),
         "nspans", "rows" (the crsql_changes fields, "ts" included) and "nrows"."""
-        import torch
-        lib = L.lib()
         if not _is_torch(dec["kind"]):
             raise ValueError("buffered_spans takes CUDA tensors: the pool rows are on the device")
+        mem = Mem(dec["kind"].device)
         T, Q, E = int(dec["nneeds"]), int(dec["nseqs"]), int(dec["nents"])
         G = int(ext["version"].shape[0])
         S = int(idx["ver_off"].shape[0]) - 1
@@ -1059,45 +960,22 @@ class MergeEngine:
         r = L.BufSpansIn()
         r.nneeds, r.nseqs, r.nents, r.ngroups, r.idx_nsites, r.idx_nver = T, Q, E, G, S, NV
         r.idx_nsr, r.idx_nseg = int(idx["sr_start"].shape[0]), int(idx["seg_pool_off"].shape[0])
-        keep = []
-        fields = [(dec, "kind", "kind", np.uint8, T), (dec, "start", "start", np.uint64, T), (dec, "end", "end", np.uint64, T),
-                  (dec, "sr_off", "sr_off", np.uint64, T), (dec, "sr_n", "sr_n", np.uint64, T),
-                  (dec, "s_start", "s_start", np.uint64, Q), (dec, "s_end", "s_end", np.uint64, Q),
-                  (dec, "need_keep", "need_keep", np.uint8, T), (dec, "need_site", "need_site", np.uint32, T),
-                  (dec, "need_ent_off", "need_ent_off", np.uint64, T + 1), (sp, "in_state", "in_state", np.uint8, T),
-                  (tl, "need_host", "need_host", np.uint8, T), (ext, "grp_off", "grp_off", np.uint64, E + 1),
-                  (ext, "version", "version", np.int64, G)]
-        fields += [(idx, k, dst, dt, None) for k, dst, dt in self._BUFIDX_IN]
-        for src, k, dst, dt, cnt in fields:
-            a, p = self._in_field(src[k], dt, True, k, cnt)
-            keep.append(a)
-            setattr(r, dst, p)
+        keep = mem.fill(r, dec, (("kind", np.uint8, T), ("start", np.uint64, T), ("end", np.uint64, T),
+                                 ("sr_off", np.uint64, T), ("sr_n", np.uint64, T), ("s_start", np.uint64, Q),
+                                 ("s_end", np.uint64, Q), ("need_keep", np.uint8, T), ("need_site", np.uint32, T),
+                                 ("need_ent_off", np.uint64, T + 1)))
+        keep += mem.fill(r, sp, (("in_state", np.uint8, T),))
+        keep += mem.fill(r, tl, (("need_host", np.uint8, T),))
+        keep += mem.fill(r, ext, (("grp_off", np.uint64, E + 1), ("version", np.int64, G)))
+        keep += mem.fill(r, idx, [(k, dt, None, dst) for k, dst, dt in self._BUFIDX_IN])
         for k, n in (("last_seq", NV), ("ts", NV), ("on_device", NV), ("sr_end", r.idx_nsr), ("seg_seq0", r.idx_nseg),
                      ("seg_n", r.idx_nseg)):
             if int(idx[k].shape[0]) != n:
                 raise ValueError(f"index field {k} must hold {n} entries")
-        alloc, ptr, sync = self._two_pass_io(True, dec["kind"].device)
-        o = L.BufSpansOut()
-        nbo = alloc(T + 1, np.uint64)
-        o.need_bspan_off = ptr(nbo)
-        sync()
-        L.check(lib.corro_buffered_spans(self._h, bookie._h, C.byref(r), L.CORRO_MEM_DEVICE, C.byref(o), 0))
-        N, R = int(o.nspans), int(o.nrows)
-        res = {}
-        for k, dt in (("site", np.uint32), ("version", np.int64), ("last_seq", np.uint64), ("ts", np.uint64),
-                      ("seq_start", np.uint64), ("seq_end", np.uint64), ("row_off", np.uint64), ("row_count", np.uint64)):
-            res[k] = alloc(N, dt)
-            setattr(o, k, ptr(res[k]))
-        tdt = {1: torch.uint8, 4: torch.int32, 8: torch.int64}
-        rows = {k: torch.empty(max(R, 1), dtype=tdt[np.dtype(dt).itemsize], device=dec["kind"].device)
-                for k, dt in ROW_FIELDS.items()}
-        for k, a in rows.items():
-            setattr(o.rows, k, ptr(a))
-        sync()
-        L.check(lib.corro_buffered_spans(self._h, bookie._h, C.byref(r), L.CORRO_MEM_DEVICE, C.byref(o), 1))
-        res = {k: a[:N] for k, a in res.items()}
-        res["need_bspan_off"], res["nspans"] = nbo[:T + 1], N
-        res["rows"], res["nrows"] = {k: a[:R] for k, a in rows.items()}, R
+        res = two_pass(L.lib().corro_buffered_spans, (self._h, bookie._h, C.byref(r), mem.const), mem, L.BufSpansOut(),
+                       (("need_bspan_off", np.uint64, T + 1),), ("nspans", "nrows"),
+                       _SPANS_OUT + tuple(("rows." + k, dt, "nrows") for k, dt in ROW_FIELDS.items()))
+        res["rows"] = {k: res.pop("rows." + k) for k in ROW_FIELDS}
         return res
 
     def assemble_answers_buffered(self, dec, sp, enc, bsp, benc, tl, payload=0):
@@ -1105,50 +983,7 @@ class MergeEngine:
         and its Empty tail frames (corro_assemble_answers_buffered). bsp: buffered_spans' result (its
         "need_bspan_off"); benc: encode_changesets' result for bsp's spans and rows (None when bsp
         holds no span). The other arguments and the result are assemble_answers'."""
-        lib = L.lib()
-        on_dev = _is_torch(dec["frame_pair_off"])
-        F, NP, T = int(dec["nframes"]), int(dec["npairs"]), int(dec["nneeds"])
-        NS, NR, BS = int(sp["nspans"]), int(tl["nranges"]), int(bsp["nspans"])
-        rb = L.AssembleBufferedIn()
-        r = rb.base
-        r.nframes, r.npairs, r.nneeds, r.nspans, r.nranges, r.payload = F, NP, T, NS, NR, int(payload)
-        r.enc_nframes, r.enc_nbytes = (int(enc["nframes"]), int(enc["nbytes"])) if NS else (0, 0)
-        r.tail_nbytes = int(tl["buf"].shape[0])
-        rb.nbspans = BS
-        rb.benc_nframes, rb.benc_nbytes = (int(benc["nframes"]), int(benc["nbytes"])) if BS else (0, 0)
-        keep = []
-        fields = [(r, dec, "frame_pair_off", "frame_pair_off", np.uint64, F + 1),
-                  (r, dec, "pair_need_off", "pair_need_off", np.uint64, NP + 1),
-                  (r, dec, "need_keep", "need_keep", np.uint8, T), (r, sp, "need_span_off", "need_span_off", np.uint64, T + 1),
-                  (r, tl, "need_tail_off", "need_tail_off", np.uint64, T + 1), (r, tl, "need_host", "need_host", np.uint8, T),
-                  (r, tl, "buf", "tail_buf", np.uint8, None),
-                  (rb, bsp, "need_bspan_off", "need_bspan_off", np.uint64, T + 1)]
-        if NS:
-            fields += [(r, enc, "span_frame_off", "span_frame_off", np.uint64, NS + 1),
-                       (r, enc, "frame_off", "enc_frame_off", np.uint64, r.enc_nframes + 1),
-                       (r, enc, "buf", "enc_buf", np.uint8, r.enc_nbytes)]
-        if BS:
-            fields += [(rb, benc, "span_frame_off", "bspan_frame_off", np.uint64, BS + 1),
-                       (rb, benc, "frame_off", "benc_frame_off", np.uint64, rb.benc_nframes + 1),
-                       (rb, benc, "buf", "benc_buf", np.uint8, rb.benc_nbytes)]
-        for st, src, k, dst, dt, cnt in fields:
-            a, p = self._in_field(src[k], dt, on_dev, k, cnt)
-            keep.append(a)
-            setattr(st, dst, p)
-        alloc, ptr, sync = self._two_pass_io(on_dev, dec["frame_pair_off"].device if on_dev else None)
-        mem = L.CORRO_MEM_DEVICE if on_dev else L.CORRO_MEM_HOST
-        o = L.Assembled()
-        nao, fao, fh = alloc(T + 1, np.uint64), alloc(F + 1, np.uint64), alloc(F, np.uint8)
-        o.need_ans_off, o.frame_ans_off, o.frame_host = ptr(nao), ptr(fao), ptr(fh)
-        sync()
-        L.check(lib.corro_assemble_answers_buffered(self._h, C.byref(rb), mem, C.byref(o), 0))
-        NB = int(o.nbytes)
-        buf = alloc(NB, np.uint8)
-        o.buf = ptr(buf)
-        sync()
-        L.check(lib.corro_assemble_answers_buffered(self._h, C.byref(rb), mem, C.byref(o), 1))
-        return {"buf": buf[:NB], "need_ans_off": nao[:T + 1], "frame_ans_off": fao[:F + 1], "frame_host": fh[:F],
-                "nbytes": NB}
+        return self._assemble(dec, sp, enc, tl, payload, bsp, benc)
 
     # ---- sync need diff -------------------------------------------------------------------
     def compute_needs(self, entries):

@@ -14,7 +14,9 @@ import struct
 import numpy as np
 
 from . import _lib as L
+from ._twopass import Mem, TwoPass
 from .agent import Change, ChangeV1, Empty, Full
+from .engine import SPAN_KEYS
 from .sync import Full as NeedFull, Partial as NeedPartial
 
 MAX_CHANGES_BYTES_PER_MESSAGE = 8 * 1024   # peer/mod.rs:365
@@ -423,12 +425,12 @@ def device_buffered(agent, dev):
     return {"buf_off": up(buf_off), "buf_version": up(bv)}
 
 
-_BUFIDX_FIELDS = (("ver_off", np.uint64, "nsites1"), ("version", np.uint64, "nver"), ("last_seq", np.int64, "nver"),
-                  ("ts", np.uint64, "nver"), ("on_device", np.uint8, "nver"), ("sr_off", np.uint64, "nver1"),
-                  ("sr_start", np.uint64, "nsr"), ("sr_end", np.uint64, "nsr"), ("seg_off", np.uint64, "nver1"),
+_BUFIDX_FIELDS = (("ver_off", np.uint64, "nsites", 1, 1), ("version", np.uint64, "nver"), ("last_seq", np.int64, "nver"),
+                  ("ts", np.uint64, "nver"), ("on_device", np.uint8, "nver"), ("sr_off", np.uint64, "nver", 1, 1),
+                  ("sr_start", np.uint64, "nsr"), ("sr_end", np.uint64, "nsr"), ("seg_off", np.uint64, "nver", 1, 1),
                   ("seg_pool_off", np.uint64, "nseg"), ("seg_seq0", np.uint32, "nseg"), ("seg_n", np.uint32, "nseg"),
-                  ("tail_gap_off", np.uint64, "nsites1"), ("tail_gap_start", np.uint64, "ntail_gap"),
-                  ("tail_gap_end", np.uint64, "ntail_gap"), ("host_buf_off", np.uint64, "nsites1"),
+                  ("tail_gap_off", np.uint64, "nsites", 1, 1), ("tail_gap_start", np.uint64, "ntail_gap"),
+                  ("tail_gap_end", np.uint64, "ntail_gap"), ("host_buf_off", np.uint64, "nsites", 1, 1),
                   ("host_buf_version", np.uint64, "nhost_buf"))
 
 
@@ -444,16 +446,10 @@ def buffered_index(agent):
     ids = agent.engine.site_ids()
     S = len(ids)
     raw = np.frombuffer(b"".join(ids), np.uint8).copy() if S else np.zeros(1, np.uint8)
-    o = L.BufferedIndex()
-    L.check(L.lib().corro_bookie_buffered_index(agent.bookie._h, raw.ctypes.data, S, C.byref(o), 0))
-    tot = {k: int(getattr(o, k)) for k in ("nver", "nsr", "nseg", "ntail_gap", "nhost_buf")}
-    tot["nsites1"], tot["nver1"] = S + 1, tot["nver"] + 1
-    res = {}
-    for k, dt, size in _BUFIDX_FIELDS:
-        res[k] = np.zeros(max(tot[size], 1), dt)
-        setattr(o, k, res[k].ctypes.data)
-    L.check(L.lib().corro_bookie_buffered_index(agent.bookie._h, raw.ctypes.data, S, C.byref(o), 1))
-    return {k: res[k][:tot[size]] for k, _dt, size in _BUFIDX_FIELDS}
+    tp = TwoPass(L.lib().corro_bookie_buffered_index, (agent.bookie._h, raw.ctypes.data, S), Mem(), L.BufferedIndex())
+    tp.run(0)
+    tp.run(1, _BUFIDX_FIELDS, {**tp.totals(("nver", "nsr", "nseg", "ntail_gap", "nhost_buf")), "nsites": S})
+    return tp.result()
 
 
 def device_buffered_index(agent, dev):
@@ -463,7 +459,7 @@ def device_buffered_index(agent, dev):
     tensors}. All of it goes up in one copy."""
     import torch
     h = buffered_index(agent)
-    names = [k for k, _dt, _s in _BUFIDX_FIELDS]
+    names = [f[0] for f in _BUFIDX_FIELDS]
     off, total = {}, 0
     for k in names:                                            # one staging buffer, 8-byte aligned slices
         off[k] = total
@@ -479,26 +475,52 @@ def device_buffered_index(agent, dev):
     return {"host": h, "dev": {k: t[k] for k in names[:12]}, "book": book}
 
 
-def handle_request_frames_buffered(agent, buf, frame_off, max_buf_size=MAX_CHANGES_BYTES_PER_MESSAGE, payload=0,
-                                   cluster_id=0, timings=None):
-    """handle_request_frames_assembled with the buffered (partial) versions served from the device row
-    pool: the same arguments, the same (frame_status, answers), byte for byte.
+# ---- serving request frames: one pipeline, three ways to finish it ------------------------------
 
-    A need whose buffered versions all lie in the bookie's pool (what process_frames buffers from
-    canonical partial changesets) no longer goes back to the host walk, which would read the
-    version's rows out of the pool for good. Stages: decode -> extract -> spans -> encode -> tails
-    against device_buffered_index's derived books (the pool versions count as gaps there, so only a
-    need that touches a host-row version keeps need_host) -> buffered_spans (the buffered chunks as
-    spans, their rows gathered from the pool) -> a second encode -> assemble_answers_buffered (per
-    need: state frames, buffered frames, Empty frames). The request screen keeps the real gaps. A need
-    still flagged need_host takes _bookie_messages, spliced in at need_ans_off[t + 1] as in
-    handle_request_frames_assembled. timings: that function's keys plus "buffered" (buffered_spans
-    and the second encode; the index call counts under "tails")."""
+# decode_requests' arrays the host walk of a need reads
+_NEED_KEYS = ("frame_pair_off", "pair_need_off", "pair_actor", "kind", "start", "end", "sr_off", "sr_n", "s_start",
+              "s_end", "need_keep", "need_ent_off")
+
+
+def _frame_messages(msgs, payload, cluster_id):
+    """ChangeV1 messages as the length-delimited frames of a payload kind, back to back."""
+    from . import wire
+    if payload == wire.PAYLOAD_SYNC:
+        return wire.frames(msgs, wire.PAYLOAD_SYNC)
+    return b"".join(wire.frame(wire.encode_uni_change(cv, cluster_id)) for cv in msgs)
+
+
+def _to_host(*parts):
+    """Read back the named arrays of each (result dict, keys), in the order given, into one dict."""
+    return {k: src[k].cpu().numpy() for src, keys in parts for k in keys}
+
+
+def _host_need_frames(agent, h, t, actor, site_ids, max_buf_size, payload, cluster_id):
+    """What the host bookie answers to decoded need t, framed: h holds the host copies of _NEED_KEYS,
+    of need_spans' "in_state" and of the extraction's "grp_off" / "version" (the versions a Full need
+    found in the state)."""
+    k = int(h["need_ent_off"][t])
+    if h["kind"][t] == 0:
+        need = NeedFull(int(h["start"][t]), int(h["end"][t]))
+        found = {int(v) for v in h["version"][int(h["grp_off"][k]):int(h["grp_off"][k + 1])]}
+    else:
+        q0 = int(h["sr_off"][t])
+        need = NeedPartial(int(h["start"][t]), tuple((int(h["s_start"][q]), int(h["s_end"][q]))
+                                                     for q in range(q0, q0 + int(h["sr_n"][t]))))
+        found = set()
+    msgs = _bookie_messages(agent, actor, need, found, bool(h["in_state"][t]), site_ids, max_buf_size)
+    return _frame_messages(msgs, payload, cluster_id)
+
+
+def _request_front(agent, buf, frame_off, max_buf_size, payload, cluster_id, timings):
+    """The stages every request path starts with: the book, decode + screen, and unless no need is
+    left the extraction, the spans and their encoding. Returns the stage results: lap (the stage timer:
+    lap(name) adds the seconds since the last lap to timings[name], with the device idle), dev, book,
+    dec, status, answers (b"" per frame) and ext, sp, enc -- ext is None when nothing is left to serve."""
     import time
+    from types import SimpleNamespace
 
     import torch
-
-    from . import wire
     eng = agent.engine
     dev = torch.device("cuda", eng.device)
     t0 = time.perf_counter()
@@ -519,29 +541,27 @@ def handle_request_frames_buffered(agent, buf, frame_off, max_buf_size=MAX_CHANG
     lap("book")
     dec = eng.decode_requests(buf, frame_off, book)
     lap("decode")
-    status = dec["frame_status"].cpu().numpy()
-    F, T = dec["nframes"], dec["nneeds"]
-    answers = [b""] * F
-    if T == 0 or dec["nents"] == 0:
-        return status, answers
-    ext = eng.extract_changes({"site": dec["ent_site"], "start": dec["ent_start"], "end": dec["ent_end"],
-                               "seq_start": dec["ent_seq_start"], "seq_end": dec["ent_seq_end"]})
+    st = SimpleNamespace(lap=lap, dev=dev, book=book, dec=dec, status=dec["frame_status"].cpu().numpy(),
+                         answers=[b""] * dec["nframes"], ext=None)
+    if dec["nneeds"] == 0 or dec["nents"] == 0:
+        return st
+    st.ext = eng.extract_changes({"site": dec["ent_site"], "start": dec["ent_start"], "end": dec["ent_end"],
+                                  "seq_start": dec["ent_seq_start"], "seq_end": dec["ent_seq_end"]})
     lap("extract")
-    sp = eng.need_spans(dec, ext)
+    st.sp = eng.need_spans(dec, st.ext)
     lap("spans")
-    span_keys = ("site", "version", "last_seq", "ts", "seq_start", "seq_end", "row_off", "row_count")
-    enc = eng.encode_changesets({k: sp[k] for k in span_keys}, ext["rows"], max_buf_size, payload, cluster_id)
+    st.enc = eng.encode_changesets({k: st.sp[k] for k in SPAN_KEYS}, st.ext["rows"], max_buf_size, payload, cluster_id)
     lap("encode")
-    idx = device_buffered_index(agent, dev)
-    tl = eng.need_tails(dec, ext, sp, idx["book"], payload, cluster_id)
-    lap("tails")
-    bsp = eng.buffered_spans(agent.bookie, dec, ext, sp, tl, idx["dev"])
-    benc = None
-    if bsp["nspans"]:
-        benc = eng.encode_changesets({k: bsp[k] for k in span_keys}, bsp["rows"], max_buf_size, payload, cluster_id)
-    lap("buffered")
-    asm = eng.assemble_answers_buffered(dec, sp, enc, bsp, benc, tl, payload)
-    lap("assemble")
+    return st
+
+
+def _join_assembled(agent, st, tl, asm, max_buf_size, payload, cluster_id):
+    """The answers from assemble_answers' buffer: one copy into a pinned staging tensor and one slice per
+    frame. Only when a frame holds a host need (frame_host) are the need arrays read back: that frame's
+    needs are walked, sliced by need_ans_off, and the host bookie's frames go in after each host need's
+    encoded piece."""
+    import torch
+    eng = agent.engine
     fao, fhost = asm["frame_ans_off"].cpu().numpy(), asm["frame_host"].cpu().numpy()
     pinned = getattr(eng, "_answer_staging", None)             # pinned, kept with the engine and grown
     if pinned is None or pinned.numel() < asm["nbytes"]:
@@ -550,16 +570,14 @@ def handle_request_frames_buffered(agent, buf, frame_off, max_buf_size=MAX_CHANG
     out = memoryview(pinned.numpy())[:asm["nbytes"]]
     hosted = np.flatnonzero(fhost)
     if len(hosted):                                            # what the host bookie's walk needs
-        h = {k: dec[k].cpu().numpy() for k in ("frame_pair_off", "pair_need_off", "pair_actor", "kind", "start", "end",
-                                               "sr_off", "sr_n", "s_start", "s_end", "need_keep", "need_ent_off")}
-        ins, need_host = sp["in_state"].cpu().numpy(), tl["need_host"].cpu().numpy()
-        grp_off, versions = ext["grp_off"].cpu().numpy(), ext["version"].cpu().numpy()
-        nao = asm["need_ans_off"].cpu().numpy()
-    lap("readback")
+        h = _to_host((st.dec, _NEED_KEYS), (st.sp, ("in_state",)), (tl, ("need_host",)),
+                     (st.ext, ("grp_off", "version")), (asm, ("need_ans_off",)))
+        nao = h["need_ans_off"]
+    st.lap("readback")
     for f in np.flatnonzero(fhost == 0):
         a, b = int(fao[f]), int(fao[f + 1])
         if b > a:
-            answers[f] = bytes(out[a:b])
+            st.answers[f] = bytes(out[a:b])
     if len(hosted):
         site_ids = dict(enumerate(eng.site_ids()))
         actors = h["pair_actor"].tobytes()
@@ -570,28 +588,47 @@ def handle_request_frames_buffered(agent, buf, frame_off, max_buf_size=MAX_CHANG
             t0n, t1n = int(h["pair_need_off"][p]), int(h["pair_need_off"][p + 1])
             lo = int(nao[t0n])                                 # the device bytes not yet taken
             for t in range(t0n, t1n):
-                if not h["need_keep"][t] or not need_host[t]:
+                if not h["need_keep"][t] or not h["need_host"][t]:
                     continue
                 parts.append(bytes(out[lo:int(nao[t + 1])]))   # up to and with this need's encoded piece
                 lo = int(nao[t + 1])
-                k = int(h["need_ent_off"][t])
-                if h["kind"][t] == 0:
-                    need = NeedFull(int(h["start"][t]), int(h["end"][t]))
-                    found = {int(v) for v in versions[int(grp_off[k]):int(grp_off[k + 1])]}
-                else:
-                    q0 = int(h["sr_off"][t])
-                    need = NeedPartial(int(h["start"][t]), tuple((int(h["s_start"][q]), int(h["s_end"][q]))
-                                                                 for q in range(q0, q0 + int(h["sr_n"][t]))))
-                    found = set()
-                msgs = _bookie_messages(agent, actor, need, found, bool(ins[t]), site_ids, max_buf_size)
-                if payload == wire.PAYLOAD_SYNC:
-                    parts.append(wire.frames(msgs, wire.PAYLOAD_SYNC))
-                else:
-                    parts.append(b"".join(wire.frame(wire.encode_uni_change(cv, cluster_id)) for cv in msgs))
+                parts.append(_host_need_frames(agent, h, t, actor, site_ids, max_buf_size, payload, cluster_id))
             parts.append(bytes(out[lo:int(nao[t1n])]))
-        answers[f] = b"".join(parts)
-    lap("bookie")
-    return status, answers
+        st.answers[f] = b"".join(parts)
+    st.lap("bookie")
+    return st.status, st.answers
+
+
+def handle_request_frames_buffered(agent, buf, frame_off, max_buf_size=MAX_CHANGES_BYTES_PER_MESSAGE, payload=0,
+                                   cluster_id=0, timings=None):
+    """handle_request_frames_assembled with the buffered (partial) versions served from the device row
+    pool: the same arguments, the same (frame_status, answers), byte for byte.
+
+    A need whose buffered versions all lie in the bookie's pool (what process_frames buffers from
+    canonical partial changesets) no longer goes back to the host walk, which would read the
+    version's rows out of the pool for good. Stages: decode -> extract -> spans -> encode -> tails
+    against device_buffered_index's derived books (the pool versions count as gaps there, so only a
+    need that touches a host-row version keeps need_host) -> buffered_spans (the buffered chunks as
+    spans, their rows gathered from the pool) -> a second encode -> assemble_answers_buffered (per
+    need: state frames, buffered frames, Empty frames). The request screen keeps the real gaps. A need
+    still flagged need_host takes _bookie_messages, spliced in at need_ans_off[t + 1] as in
+    handle_request_frames_assembled. timings: that function's keys plus "buffered" (buffered_spans
+    and the second encode; the index call counts under "tails")."""
+    eng = agent.engine
+    st = _request_front(agent, buf, frame_off, max_buf_size, payload, cluster_id, timings)
+    if st.ext is None:
+        return st.status, st.answers
+    idx = device_buffered_index(agent, st.dev)
+    tl = eng.need_tails(st.dec, st.ext, st.sp, idx["book"], payload, cluster_id)
+    st.lap("tails")
+    bsp = eng.buffered_spans(agent.bookie, st.dec, st.ext, st.sp, tl, idx["dev"])
+    benc = None
+    if bsp["nspans"]:
+        benc = eng.encode_changesets({k: bsp[k] for k in SPAN_KEYS}, bsp["rows"], max_buf_size, payload, cluster_id)
+    st.lap("buffered")
+    asm = eng.assemble_answers_buffered(st.dec, st.sp, st.enc, bsp, benc, tl, payload)
+    st.lap("assemble")
+    return _join_assembled(agent, st, tl, asm, max_buf_size, payload, cluster_id)
 
 
 def handle_request_frames(agent, buf, frame_off, max_buf_size=MAX_CHANGES_BYTES_PER_MESSAGE, payload=0, cluster_id=0,
@@ -612,59 +649,24 @@ def handle_request_frames(agent, buf, frame_off, max_buf_size=MAX_CHANGES_BYTES_
     bookie's walk, _bookie_messages, with its fields, the versions found and in_state. timings (optional
     dict) receives the seconds per stage ("tails": device_buffered and need_tails; "bookie": the join
     and what the host bookie still answers)."""
-    import time
-
-    import torch
-
     from . import wire
     eng = agent.engine
-    dev = torch.device("cuda", eng.device)
-    t0 = time.perf_counter()
-
-    def lap(name):
-        nonlocal t0
-        if timings is not None:
-            torch.cuda.synchronize(dev)
-            t1 = time.perf_counter()
-            timings[name] = timings.get(name, 0.0) + (t1 - t0)
-            t0 = t1
-
-    if not torch.is_tensor(buf):
-        buf = torch.from_numpy(np.frombuffer(bytes(buf), np.uint8).copy()).to(dev)
-    if not torch.is_tensor(frame_off):
-        frame_off = torch.from_numpy(np.ascontiguousarray(frame_off, np.uint64).view(np.int64)).to(dev)
-    book = device_book(agent, dev)
-    lap("book")
-    dec = eng.decode_requests(buf, frame_off, book)
-    lap("decode")
-    status = dec["frame_status"].cpu().numpy()
-    F, T = dec["nframes"], dec["nneeds"]
-    answers = [b""] * F
-    if T == 0 or dec["nents"] == 0:
-        return status, answers
-    ext = eng.extract_changes({"site": dec["ent_site"], "start": dec["ent_start"], "end": dec["ent_end"],
-                               "seq_start": dec["ent_seq_start"], "seq_end": dec["ent_seq_end"]})
-    lap("extract")
-    sp = eng.need_spans(dec, ext)
-    lap("spans")
-    spans = {k: sp[k] for k in ("site", "version", "last_seq", "ts", "seq_start", "seq_end", "row_off", "row_count")}
-    enc = eng.encode_changesets(spans, ext["rows"], max_buf_size, payload, cluster_id)
-    lap("encode")
-    tl = eng.need_tails(dec, ext, sp, {**book, **device_buffered(agent, dev)}, payload, cluster_id)
-    lap("tails")
+    st = _request_front(agent, buf, frame_off, max_buf_size, payload, cluster_id, timings)
+    if st.ext is None:
+        return st.status, st.answers
+    tl = eng.need_tails(st.dec, st.ext, st.sp, {**st.book, **device_buffered(agent, st.dev)}, payload, cluster_id)
+    st.lap("tails")
     # what the host bookie's walk needs: the kept needs, the versions a Full need found, in_state
-    h = {k: dec[k].cpu().numpy() for k in ("frame_pair_off", "pair_need_off", "pair_actor", "kind", "start", "end",
-                                           "sr_off", "sr_n", "s_start", "s_end", "need_keep", "need_ent_off")}
-    nso, ins = sp["need_span_off"].cpu().numpy(), sp["in_state"].cpu().numpy()
-    grp_off, versions = ext["grp_off"].cpu().numpy(), ext["version"].cpu().numpy()
-    out = enc["buf"].cpu().numpy().tobytes()
-    fo, sfo = enc["frame_off"].cpu().numpy(), enc["span_frame_off"].cpu().numpy()
+    h = _to_host((st.dec, _NEED_KEYS), (st.sp, ("need_span_off", "in_state")), (st.ext, ("grp_off", "version")))
+    nso = h["need_span_off"]
+    out = st.enc["buf"].cpu().numpy().tobytes()
+    fo, sfo = st.enc["frame_off"].cpu().numpy(), st.enc["span_frame_off"].cpu().numpy()
     nto, need_host = tl["need_tail_off"].cpu().numpy(), tl["need_host"].cpu().numpy()
     tail, tfs = tl["buf"].cpu().numpy().tobytes(), 49 if payload == wire.PAYLOAD_SYNC else 55
-    lap("readback")
+    st.lap("readback")
     site_ids = dict(enumerate(eng.site_ids()))
     actors = h["pair_actor"].tobytes()
-    for f in range(F):
+    for f in range(len(st.answers)):
         parts = []
         for p in range(int(h["frame_pair_off"][f]), int(h["frame_pair_off"][f + 1])):
             actor = actors[16 * p:16 * p + 16]
@@ -675,23 +677,10 @@ def handle_request_frames(agent, buf, frame_off, max_buf_size=MAX_CHANGES_BYTES_
                 if not need_host[t]:                            # its Empty frames, from the device
                     parts.append(tail[tfs * int(nto[t]):tfs * int(nto[t + 1])])
                     continue
-                k = int(h["need_ent_off"][t])
-                if h["kind"][t] == 0:
-                    need = NeedFull(int(h["start"][t]), int(h["end"][t]))
-                    found = {int(v) for v in versions[int(grp_off[k]):int(grp_off[k + 1])]}
-                else:
-                    q0 = int(h["sr_off"][t])
-                    need = NeedPartial(int(h["start"][t]), tuple((int(h["s_start"][q]), int(h["s_end"][q]))
-                                                                 for q in range(q0, q0 + int(h["sr_n"][t]))))
-                    found = set()
-                msgs = _bookie_messages(agent, actor, need, found, bool(ins[t]), site_ids, max_buf_size)
-                if payload == wire.PAYLOAD_SYNC:
-                    parts.append(wire.frames(msgs, wire.PAYLOAD_SYNC))
-                else:
-                    parts.append(b"".join(wire.frame(wire.encode_uni_change(cv, cluster_id)) for cv in msgs))
-        answers[f] = b"".join(parts)
-    lap("bookie")
-    return status, answers
+                parts.append(_host_need_frames(agent, h, t, actor, site_ids, max_buf_size, payload, cluster_id))
+        st.answers[f] = b"".join(parts)
+    st.lap("bookie")
+    return st.status, st.answers
 
 
 def handle_request_frames_assembled(agent, buf, frame_off, max_buf_size=MAX_CHANGES_BYTES_PER_MESSAGE, payload=0,
@@ -707,98 +696,15 @@ def handle_request_frames_assembled(agent, buf, frame_off, max_buf_size=MAX_CHAN
     need_ans_off, and _bookie_messages' frames go in after each host need's encoded piece. timings: the
     keys of handle_request_frames plus "assemble"; the read-backs count under "readback" and the
     remaining join under "bookie"."""
-    import time
-
-    import torch
-
-    from . import wire
     eng = agent.engine
-    dev = torch.device("cuda", eng.device)
-    t0 = time.perf_counter()
-
-    def lap(name):
-        nonlocal t0
-        if timings is not None:
-            torch.cuda.synchronize(dev)
-            t1 = time.perf_counter()
-            timings[name] = timings.get(name, 0.0) + (t1 - t0)
-            t0 = t1
-
-    if not torch.is_tensor(buf):
-        buf = torch.from_numpy(np.frombuffer(bytes(buf), np.uint8).copy()).to(dev)
-    if not torch.is_tensor(frame_off):
-        frame_off = torch.from_numpy(np.ascontiguousarray(frame_off, np.uint64).view(np.int64)).to(dev)
-    book = device_book(agent, dev)
-    lap("book")
-    dec = eng.decode_requests(buf, frame_off, book)
-    lap("decode")
-    status = dec["frame_status"].cpu().numpy()
-    F, T = dec["nframes"], dec["nneeds"]
-    answers = [b""] * F
-    if T == 0 or dec["nents"] == 0:
-        return status, answers
-    ext = eng.extract_changes({"site": dec["ent_site"], "start": dec["ent_start"], "end": dec["ent_end"],
-                               "seq_start": dec["ent_seq_start"], "seq_end": dec["ent_seq_end"]})
-    lap("extract")
-    sp = eng.need_spans(dec, ext)
-    lap("spans")
-    spans = {k: sp[k] for k in ("site", "version", "last_seq", "ts", "seq_start", "seq_end", "row_off", "row_count")}
-    enc = eng.encode_changesets(spans, ext["rows"], max_buf_size, payload, cluster_id)
-    lap("encode")
-    tl = eng.need_tails(dec, ext, sp, {**book, **device_buffered(agent, dev)}, payload, cluster_id)
-    lap("tails")
-    asm = eng.assemble_answers(dec, sp, enc, tl, payload)
-    lap("assemble")
-    fao, fhost = asm["frame_ans_off"].cpu().numpy(), asm["frame_host"].cpu().numpy()
-    pinned = getattr(eng, "_answer_staging", None)             # pinned, kept with the engine and grown
-    if pinned is None or pinned.numel() < asm["nbytes"]:
-        pinned = eng._answer_staging = torch.empty(max(asm["nbytes"], 1), dtype=torch.uint8, pin_memory=True)
-    pinned[:asm["nbytes"]].copy_(asm["buf"])
-    out = memoryview(pinned.numpy())[:asm["nbytes"]]
-    hosted = np.flatnonzero(fhost)
-    if len(hosted):                                            # what the host bookie's walk needs
-        h = {k: dec[k].cpu().numpy() for k in ("frame_pair_off", "pair_need_off", "pair_actor", "kind", "start", "end",
-                                               "sr_off", "sr_n", "s_start", "s_end", "need_keep", "need_ent_off")}
-        ins, need_host = sp["in_state"].cpu().numpy(), tl["need_host"].cpu().numpy()
-        grp_off, versions = ext["grp_off"].cpu().numpy(), ext["version"].cpu().numpy()
-        nao = asm["need_ans_off"].cpu().numpy()
-    lap("readback")
-    for f in np.flatnonzero(fhost == 0):
-        a, b = int(fao[f]), int(fao[f + 1])
-        if b > a:
-            answers[f] = bytes(out[a:b])
-    if len(hosted):
-        site_ids = dict(enumerate(eng.site_ids()))
-        actors = h["pair_actor"].tobytes()
-    for f in hosted:
-        parts = []
-        for p in range(int(h["frame_pair_off"][f]), int(h["frame_pair_off"][f + 1])):
-            actor = actors[16 * p:16 * p + 16]
-            t0n, t1n = int(h["pair_need_off"][p]), int(h["pair_need_off"][p + 1])
-            lo = int(nao[t0n])                                 # the device bytes not yet taken
-            for t in range(t0n, t1n):
-                if not h["need_keep"][t] or not need_host[t]:
-                    continue
-                parts.append(bytes(out[lo:int(nao[t + 1])]))   # up to and with this need's encoded piece
-                lo = int(nao[t + 1])
-                k = int(h["need_ent_off"][t])
-                if h["kind"][t] == 0:
-                    need = NeedFull(int(h["start"][t]), int(h["end"][t]))
-                    found = {int(v) for v in versions[int(grp_off[k]):int(grp_off[k + 1])]}
-                else:
-                    q0 = int(h["sr_off"][t])
-                    need = NeedPartial(int(h["start"][t]), tuple((int(h["s_start"][q]), int(h["s_end"][q]))
-                                                                 for q in range(q0, q0 + int(h["sr_n"][t]))))
-                    found = set()
-                msgs = _bookie_messages(agent, actor, need, found, bool(ins[t]), site_ids, max_buf_size)
-                if payload == wire.PAYLOAD_SYNC:
-                    parts.append(wire.frames(msgs, wire.PAYLOAD_SYNC))
-                else:
-                    parts.append(b"".join(wire.frame(wire.encode_uni_change(cv, cluster_id)) for cv in msgs))
-            parts.append(bytes(out[lo:int(nao[t1n])]))
-        answers[f] = b"".join(parts)
-    lap("bookie")
-    return status, answers
+    st = _request_front(agent, buf, frame_off, max_buf_size, payload, cluster_id, timings)
+    if st.ext is None:
+        return st.status, st.answers
+    tl = eng.need_tails(st.dec, st.ext, st.sp, {**st.book, **device_buffered(agent, st.dev)}, payload, cluster_id)
+    st.lap("tails")
+    asm = eng.assemble_answers(st.dec, st.sp, st.enc, tl, payload)
+    st.lap("assemble")
+    return _join_assembled(agent, st, tl, asm, max_buf_size, payload, cluster_id)
 
 
 def handle_needs_frames(agent, needs, max_buf_size=MAX_CHANGES_BYTES_PER_MESSAGE, payload=0, cluster_id=0):
@@ -812,8 +718,6 @@ def handle_needs_frames(agent, needs, max_buf_size=MAX_CHANGES_BYTES_PER_MESSAGE
     finished bytes. The host bookie's messages (buffered versions, Empty ranges) are a handful per
     need: they take the host encoder and follow the need's device frames, as handle_needs orders them."""
     import torch
-
-    from . import wire
     eng = agent.engine
     ent_site, ent_s, ent_e, ent_ss, ent_se = [], [], [], [], []
     plan = []
@@ -882,9 +786,5 @@ def handle_needs_frames(agent, needs, max_buf_size=MAX_CHANGES_BYTES_PER_MESSAGE
     out_all = []
     for i, (actor, need) in enumerate(needs):
         msgs = _bookie_messages(agent, actor, need, found[i], in_state[i], site_ids, max_buf_size)
-        if payload == wire.PAYLOAD_SYNC:
-            tail = wire.frames(msgs, wire.PAYLOAD_SYNC)
-        else:
-            tail = b"".join(wire.frame(wire.encode_uni_change(cv, cluster_id)) for cv in msgs)
-        out_all.append(dev_bytes[i] + tail)
+        out_all.append(dev_bytes[i] + _frame_messages(msgs, payload, cluster_id))
     return out_all

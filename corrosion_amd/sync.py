@@ -12,6 +12,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib as L
+from ._twopass import Mem, TwoPass, two_pass
 
 
 @dataclass(frozen=True)
@@ -304,8 +305,8 @@ def decode(res, index, npairs):
 
 _REQ_IN = ("site", "need_off", "kind", "start", "end", "sr_off", "sr_n", "s_start", "s_end", "grp_ent_off",
            "grp_session")
-_REQ_OUT = (("buf", "uint8", "nbytes", 0), ("frame_off", "int64", "nframes", 1), ("frame_entry", "int64", "nframes", 0),
-            ("frame_round", "int32", "nframes", 0), ("frame_needs", "int32", "nframes", 0))
+_REQ_OUT = (("buf", np.uint8, "nbytes"), ("frame_off", np.int64, "nframes", 1, 1), ("frame_entry", np.int64, "nframes"),
+            ("frame_round", np.int32, "nframes"), ("frame_needs", np.int32, "nframes"))
 
 
 def requests_csr(sessions, site_of):
@@ -344,44 +345,18 @@ def _plan_requests(engine, arr, chunk, drain, device):
     """corro_plan_requests, both passes, on host numpy arrays or (device=True) CUDA tensors keyed like
     corro_request_in. Returns nframes, nbytes, grp_frame_off, buf, frame_off, frame_entry, frame_round,
     frame_needs in the same kind of memory; with device arrays only the two totals reach the host."""
-    lib = L.lib()
-    if device:
-        import torch
-        dev = arr["need_off"].device
-        count = lambda a: int(a.numel())
-        ptr = lambda a: a.data_ptr() if a.numel() else None
-        new = lambda m, dt: torch.empty(max(m, 1), dtype=getattr(torch, dt), device=dev)
-    else:
-        count = lambda a: int(a.size)
-        ptr = lambda a: a.ctypes.data if a.size else None
-        new = lambda m, dt: np.zeros(max(m, 1), dtype=dt)
+    mem = Mem(arr["need_off"].device) if device else Mem()
+    if not device:
         want = {"site": np.uint32, "kind": np.uint8}
         arr = {k: np.ascontiguousarray(arr[k], dtype=want.get(k, np.uint64)) for k in _REQ_IN}
     r = L.RequestIn()
-    r.n = count(arr["site"])
-    r.nneeds, r.nseqs, r.ngroups = count(arr["kind"]), count(arr["s_start"]), count(arr["grp_session"])
+    r.n = mem.count(arr["site"])
+    r.nneeds, r.nseqs, r.ngroups = mem.count(arr["kind"]), mem.count(arr["s_start"]), mem.count(arr["grp_session"])
     r.chunk_size, r.drain = chunk, drain
     for k in _REQ_IN:
-        setattr(r, k, ptr(arr[k]))
-    mem = L.CORRO_MEM_DEVICE if device else L.CORRO_MEM_HOST
-    o = L.Requests()
-    res = {"grp_frame_off": new(r.ngroups + 1, "int64")}
-    o.grp_frame_off = ptr(res["grp_frame_off"])
-    if device:
-        torch.cuda.current_stream().synchronize()
-    L.check(lib.corro_plan_requests(engine._h, C.byref(r), mem, C.byref(o), 0))
-    sizes = {"nframes": o.nframes, "nbytes": o.nbytes}
-    for k, dt, size, extra in _REQ_OUT:
-        res[k] = new(sizes[size] + extra, dt)
-        setattr(o, k, ptr(res[k]))
-    if device:
-        torch.cuda.current_stream().synchronize()
-    L.check(lib.corro_plan_requests(engine._h, C.byref(r), mem, C.byref(o), 1))
-    for k, _dt, size, extra in _REQ_OUT:
-        res[k] = res[k][:sizes[size] + extra]
-    res["grp_frame_off"] = res["grp_frame_off"][:r.ngroups + 1]
-    res.update(sizes)
-    return res
+        setattr(r, k, mem.ptr(arr[k]))
+    return two_pass(L.lib().corro_plan_requests, (engine._h, C.byref(r), mem.const), mem, L.Requests(),
+                    (("grp_frame_off", np.int64, r.ngroups + 1),), ("nframes", "nbytes"), _REQ_OUT)
 
 
 def plan_requests_device(engine, needs, site, grp_ent_off, grp_session, chunk=10, drain=10):
@@ -419,14 +394,17 @@ def plan_sync_requests(engine, sessions, chunk=10, drain=10):
 
 
 _ENT_KEYS = tuple(k for k, _ in L.SyncEntries._fields_[1:])
-# corro_statedec_out's arrays: name -> (element type, total its length comes from, extra elements)
-_STATE_FRAME = (("frame_status", "int32", 1), ("frame_actor", "uint8", 16), ("frame_has_ts", "uint8", 1),
-                ("frame_ts", "int64", 1))
+# corro_statedec_out's arrays as output tables (see _twopass): pass 0's, then pass 1's over the totals
+_STATE_HEAD_OUT = (("frame_status", np.int32, "nframes"), ("frame_actor", np.uint8, "nframes", 16, 0),
+                   ("frame_has_ts", np.uint8, "nframes"), ("frame_ts", np.int64, "nframes"),
+                   ("pair_status", np.uint8, "npairs"), ("pair_ent_off", np.int64, "npairs", 1, 1))
 _STATE_ENT = {"their_head": ("n", 0), "our_head": ("n", 0), "tn_off": ("n", 1), "tn_start": ("ntn", 0), "tn_end": ("ntn", 0),
               "tp_off": ("n", 1), "tp_ver": ("ntp", 0), "tps_off": ("ntp", 1), "tps_start": ("ntps", 0),
               "tps_end": ("ntps", 0), "on_off": ("n", 1), "on_start": ("non", 0), "on_end": ("non", 0),
               "op_off": ("n", 1), "op_ver": ("nop", 0), "ops_off": ("nop", 1), "ops_start": ("nops", 0),
               "ops_end": ("nops", 0)}
+_STATE_ENT_OUT = tuple((k, np.int64, tot, 1, extra) for k, (tot, extra) in _STATE_ENT.items()) + (
+    ("entry_pair", np.int32, "n"), ("entry_site", np.int32, "n"), ("entry_actor", np.uint8, "n", 16, 0))
 _STATE_TOTALS = ("n", "ntn", "ntp", "ntps", "non", "nop", "nops", "nunregistered")
 
 
@@ -434,73 +412,42 @@ class _StateFrames:
     """corro_decode_states over one set of frames and pairs: pass 0 once, pass 1 as often as asked."""
 
     def __init__(self, engine, buf, frame_off, pairs, device):
-        self.engine, self.device = engine, device
         if device:
             import torch
-            self.torch = torch
-            dev = buf.device
+            mem = Mem(buf.device)
             npdt = {torch.uint8: np.uint8, torch.int32: np.int32, torch.int64: np.int64}
-            as_t = lambda a, dt: a.to(device=dev, dtype=dt).contiguous() if hasattr(a, "to") else torch.from_numpy(
-                np.asarray(a).astype(npdt[dt])).to(dev)
-            self.buf = as_t(buf, torch.uint8)
-            self.frame_off = as_t(frame_off, torch.int64)
+            as_t = lambda a, dt: a.to(device=mem.dev, dtype=dt).contiguous() if hasattr(a, "to") else torch.from_numpy(
+                np.asarray(a).astype(npdt[dt])).to(mem.dev)
+            buf, frame_off = as_t(buf, torch.uint8), as_t(frame_off, torch.int64)
             pr = as_t(pairs, torch.int32).reshape(-1, 2)
-            self.ours, self.theirs = pr[:, 0].contiguous(), pr[:, 1].contiguous()
-            self.count = lambda a: int(a.numel())
-            self.ptr = lambda a: a.data_ptr() if a.numel() else None
-            self.new = lambda m, dt: torch.empty(max(m, 1), dtype=getattr(torch, dt), device=dev)
+            ours, theirs = pr[:, 0].contiguous(), pr[:, 1].contiguous()
         else:
-            self.buf = np.frombuffer(bytes(buf), np.uint8) if isinstance(buf, (bytes, bytearray)) else np.ascontiguousarray(
+            mem = Mem()
+            buf = np.frombuffer(bytes(buf), np.uint8) if isinstance(buf, (bytes, bytearray)) else np.ascontiguousarray(
                 buf, np.uint8)
-            self.frame_off = np.ascontiguousarray(frame_off, np.uint64)
+            frame_off = np.ascontiguousarray(frame_off, np.uint64)
             pr = np.asarray(pairs, np.int64).reshape(-1, 2)
-            self.ours, self.theirs = np.ascontiguousarray(pr[:, 0], np.uint32), np.ascontiguousarray(pr[:, 1], np.uint32)
-            self.count = lambda a: int(a.size)
-            self.ptr = lambda a: a.ctypes.data if a.size else None
-            self.new = lambda m, dt: np.zeros(max(m, 1), dtype=dt)
+            ours, theirs = np.ascontiguousarray(pr[:, 0], np.uint32), np.ascontiguousarray(pr[:, 1], np.uint32)
+        self.keep = (buf, frame_off, ours, theirs)
         r = L.StateDecIn()
-        r.buf, r.len = self.ptr(self.buf), self.count(self.buf)
-        r.nframes, r.frame_off = self.count(self.frame_off) - 1, self.ptr(self.frame_off)
-        r.npairs, r.pair_ours, r.pair_theirs = self.count(self.ours), self.ptr(self.ours), self.ptr(self.theirs)
-        self.r = r
-        self.mem = L.CORRO_MEM_DEVICE if device else L.CORRO_MEM_HOST
+        r.buf, r.len = mem.ptr(buf), mem.count(buf)
+        r.nframes, r.frame_off = mem.count(frame_off) - 1, mem.ptr(frame_off)
+        r.npairs, r.pair_ours, r.pair_theirs = mem.count(ours), mem.ptr(ours), mem.ptr(theirs)
         F, P = r.nframes, r.npairs
-        o = L.StateDecOut()
-        res = {k: self.new(F * w, dt) for k, dt, w in _STATE_FRAME}
-        res["pair_status"] = self.new(P, "uint8")
-        res["pair_ent_off"] = self.new(P + 1, "int64")
-        for k, a in res.items():
-            setattr(o, k, self.ptr(a))
-        self._call(o, 0)
-        for k, _dt, w in _STATE_FRAME:
-            res[k] = res[k][:F * w]
-        res["frame_actor"] = res["frame_actor"].reshape(F, 16)
-        res["pair_status"], res["pair_ent_off"] = res["pair_status"][:P], res["pair_ent_off"][:P + 1]
-        self.head, self.o = res, o
-        self.totals = {k: getattr(o, k) for k in _STATE_TOTALS}
-
-    def _call(self, o, which):
-        if self.device:
-            self.torch.cuda.current_stream().synchronize()
-        L.check(L.lib().corro_decode_states(self.engine._h, C.byref(self.r), self.mem, C.byref(o), which))
+        self.tp = TwoPass(L.lib().corro_decode_states, (engine._h, C.byref(r), mem.const), mem, L.StateDecOut())
+        self.o = self.tp.o
+        self.tp.run(0, _STATE_HEAD_OUT, {"nframes": F, "npairs": P})
+        self.totals = {k: getattr(self.o, k) for k in _STATE_TOTALS}
+        self.head = self.tp.result()
+        self.head["frame_actor"] = self.head["frame_actor"].reshape(F, 16)
 
     def fill(self):
         """Pass 1: the entry arrays (sites as the engine knows them now)."""
         t = self.totals
-        res = dict(self.head)
-        for k, (tot, extra) in _STATE_ENT.items():
-            res[k] = self.new(t[tot] + extra, "int64")
-        res["entry_pair"] = self.new(t["n"], "int32")
-        res["entry_site"] = self.new(t["n"], "int32")
-        res["entry_actor"] = self.new(16 * t["n"], "uint8")
-        for k in tuple(_STATE_ENT) + ("entry_pair", "entry_site", "entry_actor"):
-            setattr(self.o, k, self.ptr(res[k]))
-        self._call(self.o, 1)
-        for k, (tot, extra) in _STATE_ENT.items():
-            res[k] = res[k][:t[tot] + extra]
-        res["entry_pair"], res["entry_site"] = res["entry_pair"][:t["n"]], res["entry_site"][:t["n"]]
-        res["entry_actor"] = res["entry_actor"][:16 * t["n"]].reshape(t["n"], 16)
-        if not self.device:
+        self.tp.run(1, _STATE_ENT_OUT, t)
+        res = {**self.head, **self.tp.result()}
+        res["entry_actor"] = res["entry_actor"].reshape(t["n"], 16)
+        if not self.tp.mem.on_dev:
             res["entry_site"] = res["entry_site"].view(np.uint32)
             for k in _STATE_ENT:
                 if k != "our_head":

@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
-from .engine import _is_torch
+from ._twopass import Mem, TwoPass, _is_torch
 
 SENTINEL = "-1"
 UPDATE, DELETE = "Update", "Delete"
@@ -110,8 +110,8 @@ def _cs_records(cs, ncs, on_dev, dev):
     return rec, (int(pairs.shape[0]) if ncs is None else ncs), rec.ctypes.data
 
 
-_OUT = (("cand_change", np.uint32), ("cand_cs", np.uint32), ("cand_table", np.uint32), ("cand_pk", np.uint64),
-        ("cand_cl", np.uint32))
+_OUT = (("cand_change", np.uint32, "ncand"), ("cand_cs", np.uint32, "ncand"), ("cand_table", np.uint32, "ncand"),
+        ("cand_pk", np.uint64, "ncand"), ("cand_cl", np.uint32, "ncand"))
 
 
 def match_changes(engine, changes, impactful, cs, filters, device=None, ncs=None, timings=None):
@@ -125,45 +125,32 @@ def match_changes(engine, changes, impactful, cs, filters, device=None, ncs=None
     are [class_off[c], class_off[c + 1]) in ascending change index. timings: a dict that receives
     "pass0_ms" / "pass1_ms", the wall time of each call (a call returns with its stream idle)."""
     import time
-    lib = L.lib()
     on_dev = _is_torch(changes["pk"]) if device is None else bool(device)
-    dev = changes["pk"].device if on_dev else None
+    mem = Mem(changes["pk"].device if on_dev else None)
     n = int(changes["pk"].shape[0])
     s = L.MatchIn()
     s.n = n
-    keep = []
-    for k, src, dt in (("pk", changes["pk"], np.uint64), ("table_cid", changes["table_cid"], np.uint32),
-                       ("cl", changes["cl"], np.uint32), ("impactful", impactful, np.uint8)):
-        a, p = engine._in_field(src, dt, on_dev, k, n)
-        keep.append(a)
-        setattr(s, k, p)
-    rec, ncs, p = _cs_records(cs, ncs, on_dev, dev)
+    keep = mem.fill(s, changes, (("pk", np.uint64, n), ("table_cid", np.uint32, n), ("cl", np.uint32, n)))
+    keep += mem.fill(s, {"impactful": impactful}, (("impactful", np.uint8, n),))
+    rec, ncs, p = _cs_records(cs, ncs, on_dev, mem.dev)
     s.ncs, s.cs = ncs, (p if ncs else None)
     s.nclasses, s.nslots = filters.nclasses, filters.nslots
-    bits = filters.device_bits(dev) if on_dev else filters.bits
-    if (int(bits.numel()) if on_dev else bits.size):
-        s.col_class_bits = bits.data_ptr() if on_dev else bits.ctypes.data
-    alloc, ptr, sync = engine._two_pass_io(on_dev, dev)
-    mem = L.CORRO_MEM_DEVICE if on_dev else L.CORRO_MEM_HOST
-    o = L.MatchOut()
-    class_off = alloc(filters.nclasses + 1, np.uint64)
-    o.class_off = ptr(class_off)
-    sync()
+    bits = filters.device_bits(mem.dev) if on_dev else filters.bits
+    s.col_class_bits = mem.ptr(bits)
+    tp = TwoPass(L.lib().corro_match_changes, (engine._h, C.byref(s), mem.const), mem, L.MatchOut())
+    tp.bind((("class_off", np.uint64, filters.nclasses + 1),))
+    mem.sync()
     t0 = time.perf_counter()
-    L.check(lib.corro_match_changes(engine._h, C.byref(s), mem, C.byref(o), 0))
+    tp.call(0)
     t1 = time.perf_counter()
-    ncand = int(o.ncand)
-    res = {k: alloc(ncand, dt) for k, dt in _OUT}
-    for k, a in res.items():
-        setattr(o, k, ptr(a))
-    sync()
+    tot = tp.totals(("ncand",))
+    tp.bind(_OUT, tot)
+    mem.sync()
     t2 = time.perf_counter()
-    L.check(lib.corro_match_changes(engine._h, C.byref(s), mem, C.byref(o), 1))
+    tp.call(1)
     if timings is not None:
         timings["pass0_ms"], timings["pass1_ms"] = (t1 - t0) * 1e3, (time.perf_counter() - t2) * 1e3
-    res = {k: a[:ncand] for k, a in res.items()}
-    res["class_off"], res["ncand"] = class_off[:filters.nclasses + 1], ncand
-    return res
+    return {**tp.result(), **tot}
 
 
 def _host(a, dt):
