@@ -46,6 +46,7 @@ EXPORTS = [
     "corro_need_tails", "corro_assemble_answers",
     "corro_bookie_buffered_index", "corro_buffered_spans", "corro_assemble_answers_buffered",
     "corro_decode_states", "corro_bookie_sync_book", "corro_encode_states", "corro_match_changes",
+    "corro_bookie_save", "corro_bookie_load",
 ]
 
 CORRO_CS_FULL, CORRO_CS_EMPTY, CORRO_CS_EMPTY_SET = 0, 1, 2
@@ -252,6 +253,15 @@ class AssembleBufferedIn(C.Structure):
                 ("benc_frame_off", C.c_void_p), ("benc_buf", C.c_void_p)]
 
 
+_IMAGE_BOOKS = ("actor_ids", "max", "gap_off", "gap_start", "gap_end", "seq_off", "seq_version", "seq_start", "seq_end",
+                "seq_last", "seq_ts", "site_ids")
+
+
+class BookieImage(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("nactors", "ngaps", "nseqrows")] + [("nsites", C.c_uint32), ("stamp", C.c_uint64)] + [
+        (k, C.c_void_p) for k in _IMAGE_BOOKS] + [("rows", Changes)]
+
+
 class ProcessOut(C.Structure):
     _fields_ = [("known", C.c_void_p), ("impactful", C.c_void_p), ("n_ready", C.c_uint64)]
 
@@ -395,6 +405,8 @@ def lib():
         "corro_bookie_sync_book": (i32, [vp, C.POINTER(SyncBook), i32]),
         "corro_encode_states": (i32, [vp, C.POINTER(StateEncIn), i32, C.POINTER(StateEncOut), i32]),
         "corro_match_changes": (i32, [vp, C.POINTER(MatchIn), i32, C.POINTER(MatchOut), i32]),
+        "corro_bookie_save": (i32, [vp, vp, C.POINTER(BookieImage), i32, i32]),
+        "corro_bookie_load": (i32, [vp, vp, C.POINTER(BookieImage), i32]),
         "corro_partition_ranks": (i32, [vp, C.POINTER(Changes), u32, C.POINTER(Changes), vp]),
         "corro_packed_record_bytes": (i32, [C.POINTER(Changes), vp]),
         "corro_partition_packed": (i32, [vp, C.POINTER(Changes), u32, vp, vp, vp]),

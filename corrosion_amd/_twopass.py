@@ -147,3 +147,61 @@ def two_pass(fn, lead, mem, o, pre, totals, post):
     tot = tp.totals(totals)
     tp.run(1, post, tot)
     return {**tp.result(), **tot}
+
+
+# corro_bookie_image: the books (host arrays whatever `mem` is) and the rows (in `mem`)
+IMAGE_BOOKS = (("actor_ids", np.uint8, "nactors", 16, 0), ("max", np.int64, "nactors"), ("gap_off", np.uint64, "nactors", 1, 1),
+               ("gap_start", np.uint64, "ngaps"), ("gap_end", np.uint64, "ngaps"), ("seq_off", np.uint64, "nactors", 1, 1),
+               ("seq_version", np.uint64, "nseqrows"), ("seq_start", np.uint64, "nseqrows"), ("seq_end", np.uint64, "nseqrows"),
+               ("seq_last", np.uint64, "nseqrows"), ("seq_ts", np.uint64, "nseqrows"), ("site_ids", np.uint8, "nsites", 16, 0))
+IMAGE_ROWS = (("pk", np.uint64), ("table_cid", np.uint32), ("col_version", np.int64), ("db_version", np.int64),
+              ("cl", np.uint32), ("seq", np.uint32), ("site", np.uint32), ("val0", np.uint64), ("val1", np.uint64),
+              ("val_type", np.uint8), ("val_len", np.uint8), ("ts", np.uint64))
+IMAGE_LONG = (("val_off", np.uint64, "nrows"), ("val_size", np.uint32, "nrows"), ("val_data", np.uint8, "val_data_len"))
+
+
+def save_image(fn, ctx, bk, mem):
+    """corro_bookie_save's two passes: the image's books as host arrays and its rows in `mem`, by name
+    ("rows" holds the row arrays), with the counts. fn(ctx, bk, &image, mem, pass)."""
+    o = L.BookieImage()
+    books = TwoPass(lambda c, b, op, which: fn(c, b, op, mem.const, which), (ctx, bk), Mem(), o)
+    books.run(0)
+    tot = books.totals(("nactors", "ngaps", "nseqrows", "nsites", "stamp"))
+    tot["nrows"], tot["val_data_len"] = int(o.rows.n), int(o.rows.val_data_len)
+    rows = TwoPass(None, (), mem, o)
+    rows.bind(tuple(("rows." + k, dt, "nrows") for k, dt in IMAGE_ROWS), tot)
+    if tot["val_data_len"]:
+        rows.bind(tuple(("rows." + k, dt, size) for k, dt, size in IMAGE_LONG), tot)
+    mem.sync()
+    books.run(1, IMAGE_BOOKS, tot)
+    res = {**books.result(), **tot}
+    res["actor_ids"] = res["actor_ids"].reshape(-1, 16)
+    res["site_ids"] = res["site_ids"].reshape(-1, 16)
+    res["rows"] = {k[5:]: a for k, a in rows.result().items()}
+    return res
+
+
+def load_image(fn, ctx, bk, image):
+    """corro_bookie_load of an image as save_image gives it (or one built by hand): the books are numpy
+    arrays, the rows numpy arrays or CUDA tensors. fn(ctx, bk, &image, mem)."""
+    o = L.BookieImage()
+    host = Mem()
+    na, ng, ns = len(image["max"]), len(image["gap_start"]), len(image["seq_version"])
+    nsites = int(np.asarray(image["site_ids"]).size // 16)
+    o.nactors, o.ngaps, o.nseqrows, o.nsites = na, ng, ns, nsites
+    counts = {"actor_ids": 16 * na, "max": na, "gap_off": na + 1, "gap_start": ng, "gap_end": ng, "seq_off": na + 1,
+              "seq_version": ns, "seq_start": ns, "seq_end": ns, "seq_last": ns, "seq_ts": ns, "site_ids": 16 * nsites}
+    keep = host.fill(o, {k: np.asarray(image[k]).reshape(-1) for k in counts},
+                     [(k, dt, counts[k]) for k, dt, *_ in IMAGE_BOOKS])
+    rows = image.get("rows") or {}
+    n = Mem.of(rows["pk"]).count(rows["pk"]) if "pk" in rows else 0
+    mem = Mem.of(rows["pk"]) if n else host
+    o.rows.n = n
+    if n:
+        keep += mem.fill(o.rows, rows, [(k, dt, n) for k, dt in IMAGE_ROWS])
+        if "val_data" in rows and mem.count(rows["val_data"]):
+            keep += mem.fill(o.rows, rows, [("val_off", np.uint64, n), ("val_size", np.uint32, n), ("val_data", np.uint8, None)])
+            o.rows.val_data_len = mem.count(rows["val_data"])
+    mem.sync()
+    L.check(fn(ctx, bk, C.byref(o), mem.const))
+    del keep

@@ -161,6 +161,34 @@ class Bookie:
         return book
 
 
+    def save(self, engine=None, device=False):
+        """The bookie's image (corro_bookie_save): the three bookkeeping tables and the per-actor max as
+        numpy arrays keyed like corro_bookie_image, "rows" = the __corro_buffered_changes rows sorted by
+        (site, db_version, seq) -- numpy arrays, or with device=True CUDA tensors gathered from the device
+        row pool without visiting the host. engine: the MergeEngine whose context holds the rows (None: a
+        bookie without pool rows)."""
+        from ._twopass import Mem, save_image
+        mem = Mem("cuda:%d" % engine.device) if device else Mem()
+        return save_image(L.lib().corro_bookie_save, engine._h if engine is not None else None, self._h, mem)
+
+    def load(self, image, engine=None):
+        """Load an image into this (empty) bookie (corro_bookie_load): from_conn per actor, the rows sorted
+        and cut into pool segments on the device. Without rows no engine is needed and no device is
+        touched. The fully buffered versions found are listed by take_ready."""
+        from ._twopass import load_image
+        load_image(L.lib().corro_bookie_load, engine._h if engine is not None else None, self._h, image)
+
+    def take_ready(self):
+        c = C.c_uint64()
+        L.check(L.lib().corro_bookie_take_ready(self._h, None, None, 0, C.byref(c)))
+        if c.value == 0:
+            return []
+        a = np.zeros((c.value, 16), np.uint8)
+        v = np.zeros(c.value, np.uint64)
+        L.check(L.lib().corro_bookie_take_ready(self._h, a.ctypes.data, v.ctypes.data, c.value, C.byref(c)))
+        return [(bytes(a[k]), int(v[k])) for k in range(c.value)]
+
+
 class Agent:
     """One node's writer: the device merge engine + its Bookie (agent.rs:480-482 single writer)."""
 
@@ -357,14 +385,18 @@ class Agent:
                                      ncs=dec["n_dev"])
 
     def take_ready(self):
-        c = C.c_uint64()
-        L.check(L.lib().corro_bookie_take_ready(self.bookie._h, None, None, 0, C.byref(c)))
-        if c.value == 0:
-            return []
-        a = np.zeros((c.value, 16), np.uint8)
-        v = np.zeros(c.value, np.uint64)
-        L.check(L.lib().corro_bookie_take_ready(self.bookie._h, a.ctypes.data, v.ctypes.data, c.value, C.byref(c)))
-        return [(bytes(a[k]), int(v[k])) for k in range(c.value)]
+        return self.bookie.take_ready()
+
+    def save_bookie(self, device=False):
+        """The bookie's image (Bookie.save): what a restart needs besides the exported state."""
+        return self.bookie.save(self.engine, device=device)
+
+    def load_bookie(self, image):
+        """Load a saved image into this agent's empty bookie (Bookie.load). The image's site ordinals must
+        be registered here to the same ids (register the sites and re-seed the state first); the fully
+        buffered versions found are listed by take_ready."""
+        self.bookie.load(image, self.engine)
+        self.site_ids = dict(enumerate(self.engine.site_ids()))
 
     def process_fully_buffered_changes(self, actor, version):
         r = C.c_int()

@@ -2872,3 +2872,325 @@ int corro_bookie_sync_book(corro_bookie *bk, corro_sync_book *o, int pass) {
 }
 
 }  // extern "C"
+
+// ---- the bookie's image (corro_hip.h "the bookie's image"; the device half is bookie_image.hip) ----
+namespace {
+
+// The image's host side as save builds it on both passes: the books in the image's order, the rows'
+// sources (pool pieces, host rows with their pieces), and a digest of all of it.
+struct ImageBooks {
+    std::vector<uint8_t> actor_ids, site_ids;
+    std::vector<int64_t> max;
+    std::vector<uint64_t> gap_off{0}, gap_start, gap_end, seq_off{0}, seq_version, seq_start, seq_end, seq_last, seq_ts;
+    std::vector<corro::ImgPiece> pool_pieces, host_pieces;
+    corro::ImgHostRows hrows;
+    uint64_t nrows = 0;
+    uint64_t stamp = 0;
+};
+
+struct Fnv {
+    uint64_t h = 0xcbf29ce484222325ULL;
+    void bytes(const void *p, size_t n) {
+        const uint8_t *b = static_cast<const uint8_t *>(p);
+        for (size_t i = 0; i < n; i++) h = (h ^ b[i]) * 0x100000001b3ULL;
+    }
+    template <class T> void vec(const std::vector<T> &v) {
+        const uint64_t n = v.size();
+        bytes(&n, 8);
+        if (n) bytes(v.data(), n * sizeof(T));
+    }
+};
+
+int image_books(const corro_bookie *bk, ImageBooks &B) {
+    uint32_t nsites = 0;
+    for (const auto &[id, site] : bk->site_of) nsites = std::max(nsites, site + 1);
+    B.site_ids.assign(16 * (size_t)nsites, 0);
+    for (const auto &[id, site] : bk->site_of) std::memcpy(B.site_ids.data() + 16 * (size_t)site, id.data(), 16);
+    for (const auto &[id, booked] : bk->actors) {  // ActorId byte order
+        B.actor_ids.insert(B.actor_ids.end(), id.begin(), id.end());
+        B.max.push_back(booked.has_max ? (int64_t)booked.max : -1);
+        for (const auto &r : booked.needed.ranges()) {
+            B.gap_start.push_back(r.first);
+            B.gap_end.push_back(r.second);
+        }
+        B.gap_off.push_back(B.gap_start.size());
+        auto so = bk->site_of.find(id);
+        if (so != bk->site_of.end()) {
+            const uint32_t site = so->second;
+            for (size_t i = bk->seqbook.lower({site, 0}); i < bk->seqbook.slots(); i++) {
+                const auto &x = bk->seqbook.at(i);
+                if (x.key.first != site) break;
+                if (x.dead) continue;
+                std::vector<Range> rs(x.val.ranges.begin(), x.val.ranges.end());
+                std::sort(rs.begin(), rs.end());
+                for (const Range &r : rs) {
+                    B.seq_version.push_back(x.key.second);
+                    B.seq_start.push_back(r.first);
+                    B.seq_end.push_back(r.second);
+                    B.seq_last.push_back(x.val.last_seq);
+                    B.seq_ts.push_back(x.val.ts);
+                }
+            }
+        }
+        B.seq_off.push_back(B.seq_version.size());
+    }
+    // the rows: the buffered table's keys ascend by (site, db_version); a key is pool segments or host rows
+    corro::ImgHostRows &H = B.hrows;
+    for (size_t i = 0; i < bk->buffered.slots(); i++) {
+        const auto &x = bk->buffered.at(i);
+        if (x.dead || x.val.empty()) continue;
+        if (x.val.segs.any_pending()) return fail(CORRO_E_INVALID, "the bookie holds a segment whose copy is pending");
+        for (const PoolSeg &g : x.val.segs) {
+            B.pool_pieces.push_back({g.off, B.nrows, g.n});
+            B.nrows += g.n;
+        }
+        if (!x.val.rows.empty()) {
+            B.host_pieces.push_back({H.size(), B.nrows, x.val.rows.size()});
+            B.nrows += x.val.rows.size();
+            for (const HostRow &r : x.val.rows) {
+                H.pk.push_back(r.pk); H.v0.push_back(r.v0); H.v1.push_back(r.v1); H.ts.push_back(r.ts);
+                H.cv.push_back(r.cv); H.dbv.push_back(r.dbv); H.tcid.push_back(r.tcid); H.cl.push_back(r.cl);
+                H.seq.push_back(r.seq); H.site.push_back(r.site); H.vt.push_back(r.vt); H.vl.push_back(r.vl);
+                const bool lv = is_long(r.vt, r.vl) && !r.lv.empty();
+                H.voff.push_back(lv ? H.data.size() : 0);
+                H.vsz.push_back(lv ? (uint32_t)r.lv.size() : 0);
+                if (lv) H.data.insert(H.data.end(), r.lv.begin(), r.lv.end());
+            }
+        }
+    }
+    Fnv f;
+    f.vec(B.actor_ids); f.vec(B.site_ids); f.vec(B.max); f.vec(B.gap_off); f.vec(B.gap_start); f.vec(B.gap_end);
+    f.vec(B.seq_off); f.vec(B.seq_version); f.vec(B.seq_start); f.vec(B.seq_end); f.vec(B.seq_last); f.vec(B.seq_ts);
+    for (const auto *v : {&B.pool_pieces, &B.host_pieces})
+        for (const corro::ImgPiece &p : *v) {
+            const uint64_t w[3] = {p.src, p.dst, p.n};
+            f.bytes(w, sizeof(w));
+        }
+    f.vec(H.pk); f.vec(H.v0); f.vec(H.v1); f.vec(H.ts); f.vec(H.cv); f.vec(H.dbv); f.vec(H.tcid); f.vec(H.cl);
+    f.vec(H.seq); f.vec(H.site); f.vec(H.vt); f.vec(H.vl); f.vec(H.vsz); f.vec(H.data);
+    B.stamp = f.h;
+    return CORRO_OK;
+}
+
+int bookie_save(corro_ctx *ctx, corro_bookie *bk, corro_bookie_image *o, int mem, int pass) {
+    ImageBooks B;
+    TRY_RC(image_books(bk, B));
+    const uint64_t na = B.max.size(), ng = B.gap_start.size(), ns = B.seq_version.size();
+    const uint32_t nsites = (uint32_t)(B.site_ids.size() / 16);
+    const uint64_t nd = B.hrows.data.size();
+    if (pass == 0) {
+        o->nactors = na;
+        o->ngaps = ng;
+        o->nseqrows = ns;
+        o->nsites = nsites;
+        o->stamp = B.stamp;
+        o->rows.n = B.nrows;
+        o->rows.val_data_len = nd;
+        return CORRO_OK;
+    }
+    if (o->nactors != na || o->ngaps != ng || o->nseqrows != ns || o->nsites != nsites || o->rows.n != B.nrows ||
+        o->rows.val_data_len != nd || o->stamp != B.stamp)
+        return fail(CORRO_E_INVALID, "the bookie changed since pass 0 (counts or stamp differ)");
+    const corro_changes &r = o->rows;
+    if (!o->gap_off || !o->seq_off || (na && (!o->actor_ids || !o->max)) || (ng && (!o->gap_start || !o->gap_end)) ||
+        (ns && (!o->seq_version || !o->seq_start || !o->seq_end || !o->seq_last || !o->seq_ts)) || (nsites && !o->site_ids) ||
+        (B.nrows && (!r.pk || !r.table_cid || !r.col_version || !r.db_version || !r.cl || !r.seq || !r.site || !r.val0 ||
+                     !r.val1 || !r.val_type || !r.val_len || !r.ts)) ||
+        (nd && (!r.val_off || !r.val_size || !r.val_data)))
+        return fail(CORRO_E_INVALID, "an output array is NULL");
+    const bool host_only = B.pool_pieces.empty() && mem == CORRO_MEM_HOST;
+    if (B.nrows && !host_only) {
+        if (!ctx) return fail(CORRO_E_INVALID, "NULL context: the bookie's rows lie in its device pool, or mem is the device");
+        if (corro::DevBufPool *pool = corro::bookie_pool(bk); !B.pool_pieces.empty() && !corro::bufpool_usable(ctx, pool))
+            return fail(CORRO_E_INVALID, "the bookie's row pool lies on another device than the context's");
+    }
+    // the rows first (the only part that can fail), then the books
+    if (B.nrows && host_only) {
+        const corro::ImgHostRows &H = B.hrows;  // (host keys alone: the rows are the host rows in order)
+        auto put = [&](const auto *dst, const auto &src) {
+            using T = std::remove_const_t<std::remove_pointer_t<decltype(dst)>>;
+            std::memcpy(const_cast<T *>(dst), src.data(), src.size() * sizeof(src[0]));
+        };
+        put(r.pk, H.pk); put(r.val0, H.v0); put(r.val1, H.v1); put(r.ts, H.ts); put(r.col_version, H.cv);
+        put(r.db_version, H.dbv); put(r.table_cid, H.tcid); put(r.cl, H.cl); put(r.seq, H.seq); put(r.site, H.site);
+        put(r.val_type, H.vt); put(r.val_len, H.vl);
+        if (nd) {
+            put(r.val_off, H.voff);
+            put(r.val_size, H.vsz);
+            put(r.val_data, H.data);
+        }
+    } else if (B.nrows) {
+        TRY_RC(corro::bookimg_gather(ctx, corro::bookie_pool(bk), B.pool_pieces, B.hrows, B.host_pieces, B.nrows, &r, mem));
+    }
+    auto put = [](auto *dst, const auto &src) {
+        if (!src.empty()) std::memcpy(dst, src.data(), src.size() * sizeof(src[0]));
+    };
+    put(o->actor_ids, B.actor_ids);
+    put(o->max, B.max);
+    put(o->gap_off, B.gap_off);
+    put(o->gap_start, B.gap_start);
+    put(o->gap_end, B.gap_end);
+    put(o->seq_off, B.seq_off);
+    put(o->seq_version, B.seq_version);
+    put(o->seq_start, B.seq_start);
+    put(o->seq_end, B.seq_end);
+    put(o->seq_last, B.seq_last);
+    put(o->seq_ts, B.seq_ts);
+    put(o->site_ids, B.site_ids);
+    return CORRO_OK;
+}
+
+// corro_bookie_load's body: everything is built aside and moved into the bookie at the end, so a
+// failure leaves it as corro_bookie_new made it (the pool built here is freed by the caller).
+int bookie_load(corro_ctx *ctx, corro_bookie *bk, const corro_bookie_image *im, int mem, corro::DevBufPool **pool_out) {
+    const uint64_t na = im->nactors, ng = im->ngaps, ns = im->nseqrows, nr = im->rows.n;
+    const uint32_t nsites = im->nsites;
+    const corro_changes &r = im->rows;
+    if ((na && (!im->actor_ids || !im->max || !im->gap_off || !im->seq_off)) || (ng && (!im->gap_start || !im->gap_end)) ||
+        (ns && (!im->seq_version || !im->seq_start || !im->seq_end || !im->seq_last || !im->seq_ts)) ||
+        (nsites && !im->site_ids) ||
+        (nr && (!r.pk || !r.table_cid || !r.col_version || !r.db_version || !r.cl || !r.seq || !r.site || !r.val0)))
+        return fail(CORRO_E_INVALID, "an input array is NULL");
+    if (na && (im->gap_off[0] != 0 || im->seq_off[0] != 0 || im->gap_off[na] != ng || im->seq_off[na] != ns))
+        return fail(CORRO_E_INVALID, "gap_off / seq_off do not span ngaps / nseqrows");
+    if (!na && (ng || ns)) return fail(CORRO_E_INVALID, "gaps or seq rows without an actor");
+    for (uint64_t a = 0; a < na; a++)
+        if (im->gap_off[a] > im->gap_off[a + 1] || im->gap_off[a + 1] > ng || im->seq_off[a] > im->seq_off[a + 1] ||
+            im->seq_off[a + 1] > ns)
+            return fail(CORRO_E_INVALID, "gap_off / seq_off are not monotone");
+    if (nr && !ctx) return fail(CORRO_E_INVALID, "NULL context with buffered rows: they load into the device pool");
+    std::map<ActorId, uint32_t> ord_of;  // the image's site table (the lowest ordinal of an id)
+    for (uint32_t s = 0; s < nsites; s++) ord_of.emplace(actor_of(im->site_ids + 16 * (size_t)s), s);
+    std::map<ActorId, corro::Booked> actors;
+    std::map<ActorId, uint32_t> site_of;
+    std::vector<std::pair<SeqKey, SeqBook>> books;
+    std::vector<std::pair<ActorId, uint64_t>> ready;
+    for (uint64_t a = 0; a < na; a++) {
+        const ActorId id = actor_of(im->actor_ids + 16 * a);
+        auto [it, fresh] = actors.emplace(id, corro::Booked());
+        if (!fresh) return fail(CORRO_E_INVALID, "an actor is repeated in the image");
+        corro::Booked &b = it->second;  // from_conn (agent.rs:1282-1351)
+        if (im->max[a] >= 0) {
+            b.has_max = true;
+            b.max = (uint64_t)im->max[a];
+        }
+        auto so = ord_of.find(id);
+        if (so != ord_of.end()) {
+            uint8_t reg[16];
+            if (ctx && corro::agent_site_id(ctx, so->second, reg) && std::memcmp(reg, id.data(), 16) != 0)
+                return fail(CORRO_E_INVALID, "site_ids names another id than the context has registered for an actor's ordinal");
+            site_of[id] = so->second;
+        }
+        const uint64_t s0 = im->seq_off[a], s1 = im->seq_off[a + 1];
+        if (s1 > s0 && so == ord_of.end())
+            return fail(CORRO_E_INVALID, "an actor with __corro_seq_bookkeeping rows is not in site_ids");
+        for (uint64_t k = s0; k < s1; k++) {
+            if (im->seq_start[k] > im->seq_end[k]) return fail(CORRO_E_INVALID, "a seq row with start_seq > end_seq");
+            corro::PartialVersion p;
+            p.seqs.insert(im->seq_start[k], im->seq_end[k]);
+            p.last_seq = im->seq_last[k];
+            p.ts = im->seq_ts[k];
+            b.insert_partial(im->seq_version[k], std::move(p));
+            const SeqKey key{so->second, im->seq_version[k]};
+            books.emplace_back(key, SeqBook{});
+            SeqBook &sb = books.back().second;
+            sb.ranges.push_back(Range{im->seq_start[k], im->seq_end[k]});
+            sb.last_seq = im->seq_last[k];
+            sb.ts = im->seq_ts[k];
+        }
+        for (uint64_t k = im->gap_off[a]; k < im->gap_off[a + 1]; k++) {
+            if (im->gap_start[k] > im->gap_end[k]) return fail(CORRO_E_INVALID, "a gap with start > end");
+            b.needed.insert(im->gap_start[k], im->gap_end[k]);  // (max does not come from gaps, agent.rs:1338-1342)
+        }
+        for (const auto &[v, p] : b.partials)  // run_root.rs:181-193
+            if (!p.seqs.has_gap(0, p.last_seq)) ready.emplace_back(id, v);
+    }
+    // the seq books by key: a version's rows in the order given, its first row's last_seq and ts
+    std::stable_sort(books.begin(), books.end(), [](const auto &x, const auto &y) { return x.first < y.first; });
+    FlatMap<SeqKey, SeqBook>::Entries sadd;
+    for (auto &[key, sb] : books) {
+        if (!sadd.empty() && sadd.back().key == key) sadd.back().val.ranges.push_back(sb.ranges[0]);
+        else sadd.push_back({key, std::move(sb), false});
+    }
+    // the rows: sorted, checked and cut on the device; the host builds one entry per key from the segment
+    // list and the host keys' rows
+    FlatMap<BufKey, BufEntry>::Entries badd;
+    if (nr) {
+        *pool_out = corro::bufpool_new();
+        std::vector<corro::ImgSeg> segs;
+        corro::ImgHostRows H;
+        TRY_RC(corro::bookimg_load_rows(ctx, *pool_out, &r, mem, im->site_ids, nsites, segs, H));
+        size_t g = 0, h = 0;
+        const size_t nh = H.size();
+        while (g < segs.size() || h < nh) {
+            const BufKey kg = g < segs.size() ? BufKey{segs[g].site, segs[g].dbv} : BufKey{UINT32_MAX, INT64_MAX};
+            const BufKey kh = h < nh ? BufKey{H.site[h], H.dbv[h]} : BufKey{UINT32_MAX, INT64_MAX};
+            BufEntry e;
+            if (g < segs.size() && (h >= nh || kg < kh)) {
+                for (; g < segs.size() && BufKey{segs[g].site, segs[g].dbv} == kg; g++)
+                    e.segs.insert_sorted(PoolSeg{segs[g].off, segs[g].seq0, (uint32_t)segs[g].n});
+                badd.push_back({kg, std::move(e), false});
+                continue;
+            }
+            for (; h < nh && BufKey{H.site[h], H.dbv[h]} == kh; h++) {
+                HostRow x;
+                x.pk = H.pk[h]; x.v0 = H.v0[h]; x.v1 = H.v1[h]; x.ts = H.ts[h]; x.cv = H.cv[h]; x.dbv = H.dbv[h];
+                x.tcid = H.tcid[h]; x.cl = H.cl[h]; x.seq = H.seq[h]; x.site = H.site[h]; x.vt = H.vt[h]; x.vl = H.vl[h];
+                // (a long value whose span is malformed is kept empty, as row_at keeps it)
+                if (is_long(x.vt, x.vl) && H.vsz[h] > 16 && H.voff[h] <= H.data.size() && H.vsz[h] <= H.data.size() - H.voff[h])
+                    x.lv.assign(reinterpret_cast<const char *>(H.data.data() + H.voff[h]), H.vsz[h]);
+                e.rows.push_back(std::move(x));
+            }
+            badd.push_back({kh, std::move(e), false});
+        }
+    }
+    bk->actors = std::move(actors);
+    bk->site_of = std::move(site_of);
+    bk->seqbook.merge(std::move(sadd));
+    bk->buffered.merge(std::move(badd));
+    bk->ready = std::move(ready);
+    if (*pool_out && corro::bufpool_top(*pool_out) == 0) {  // (every key stayed on the host)
+        corro::bufpool_free(*pool_out);
+        *pool_out = nullptr;
+    }
+    bk->pool = *pool_out;
+    *pool_out = nullptr;
+    return CORRO_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int corro_bookie_save(corro_ctx *ctx, corro_bookie *bk, corro_bookie_image *img, int mem, int pass) {
+    if (!bk || !img) return fail(CORRO_E_INVALID, "NULL argument");
+    if (mem != CORRO_MEM_HOST && mem != CORRO_MEM_DEVICE) return fail(CORRO_E_INVALID, "bad mem kind");
+    if (pass != 0 && pass != 1) return fail(CORRO_E_INVALID, "pass must be 0 or 1");
+    try {
+        return bookie_save(ctx, bk, img, mem, pass);
+    } catch (const std::bad_alloc &) {
+        return fail(CORRO_E_NOMEM, "host allocation failed in corro_bookie_save");
+    } catch (const std::exception &e) {
+        return fail(CORRO_E_INVALID, std::string("corro_bookie_save: ") + e.what());
+    }
+}
+
+int corro_bookie_load(corro_ctx *ctx, corro_bookie *bk, const corro_bookie_image *img, int mem) {
+    if (!bk || !img) return fail(CORRO_E_INVALID, "NULL argument");
+    if (mem != CORRO_MEM_HOST && mem != CORRO_MEM_DEVICE) return fail(CORRO_E_INVALID, "bad mem kind");
+    if (!bk->actors.empty() || bk->buffered.live() || bk->seqbook.live() || !bk->ready.empty() || bk->pool)
+        return fail(CORRO_E_INVALID, "corro_bookie_load takes an empty bookie");
+    corro::DevBufPool *pool = nullptr;
+    int rc;
+    try {
+        rc = bookie_load(ctx, bk, img, mem, &pool);
+    } catch (const std::bad_alloc &) {
+        rc = fail(CORRO_E_NOMEM, "host allocation failed in corro_bookie_load");
+    } catch (const std::exception &e) {
+        rc = fail(CORRO_E_INVALID, std::string("corro_bookie_load: ") + e.what());
+    }
+    corro::bufpool_free(pool);  // (null once the bookie owns it)
+    return rc;
+}
+
+}  // extern "C"

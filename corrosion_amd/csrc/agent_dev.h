@@ -174,6 +174,41 @@ int bufpool_append(corro_ctx *ctx, DevBufPool *p, const corro_changes *dv, std::
 // pool rows [off, off + n) to the host (no long values)
 int bufpool_read(const DevBufPool *p, uint64_t off, uint64_t n, HostSpanRows &out);
 
+// room taken at the pool's top (reserved before): *v = the pool's columns, *base = the first row taken
+int bufpool_take(corro_ctx *ctx, DevBufPool *p, uint64_t n, corro_changes *v, uint64_t *base);
+
+// ---- the bookie's image (bookie_image.hip: the device half of corro_bookie_save / corro_bookie_load) ----
+// rows [src, src + n) of a source -> rows [dst, dst + n) of the image
+struct ImgPiece {
+    uint64_t src, dst, n;
+};
+// __corro_buffered_changes rows on the host, as columns (voff / vsz index `data`; read for long values only)
+struct ImgHostRows {
+    std::vector<uint64_t> pk, v0, v1, ts, voff;
+    std::vector<int64_t> cv, dbv;
+    std::vector<uint32_t> tcid, cl, seq, site, vsz;
+    std::vector<uint8_t> vt, vl;
+    std::vector<uint8_t> data;
+    size_t size() const { return pk.size(); }
+};
+// Save: the image's `nrows` rows written through out's pointers (`mem` memory). pool_pieces name pool
+// rows, host_pieces rows of `hrows`; together their dst ranges tile [0, nrows), each list ascending by
+// dst. One output-driven gather per source; hrows.data goes to out->val_data.
+int bookimg_gather(corro_ctx *ctx, const DevBufPool *pool, const std::vector<ImgPiece> &pool_pieces,
+                   const ImgHostRows &hrows, const std::vector<ImgPiece> &host_pieces, uint64_t nrows,
+                   const corro_changes *out, int mem);
+// Load: the image's rows (`mem` memory, any order) keyed, sorted by (site, db_version, seq), checked and
+// cut into segments on the device; the canonical keys' rows gathered into `pool` (reserved here), the
+// other keys' rows brought to the host in sorted order (hrows.data = the image's val_data when one of
+// them holds a long value). segs ascend by (site, dbv, seq0). site_ids: the image's, nsites * 16 bytes.
+struct ImgSeg {
+    uint32_t site, seq0;
+    int64_t dbv;
+    uint64_t off, n;
+};
+int bookimg_load_rows(corro_ctx *ctx, DevBufPool *pool, const corro_changes *rows, int mem, const uint8_t *site_ids,
+                      uint32_t nsites, std::vector<ImgSeg> &segs, ImgHostRows &hrows);
+
 // Batched gap bookkeeping (corro_booked_insert_db_batch, gaps.hip) for a call with many actors:
 // host CSR in (per actor: booked max or -1, needed gaps, this call's versions), host arrays out
 // (per actor: new max, DELETE rows, INSERT rows, new gaps, status).

@@ -255,6 +255,15 @@ int bufpool_reserve(corro_ctx *ctx, DevBufPool *p, uint64_t need, std::vector<ui
     return CORRO_OK;
 }
 
+int bufpool_take(corro_ctx *ctx, DevBufPool *p, uint64_t n, corro_changes *v, uint64_t *base) {
+    if (!bufpool_usable(ctx, p) || !p->buf.p || p->top + n > p->cap)
+        return fail(CORRO_E_INVALID, "buffered-row pool not reserved");
+    *v = pool_view(p->buf.p, p->cap);
+    *base = p->top;
+    p->top += n;
+    return CORRO_OK;
+}
+
 // input changes -> pool rows at [top, top + sum(count)) in job order; dst written per job
 int bufpool_append(corro_ctx *ctx, DevBufPool *p, const corro_changes *dv, std::vector<PoolCopy> &jobs) {
     const uint64_t n = jobs.size();

@@ -306,6 +306,9 @@ struct corro_ctx {
     // change matching (match.hip): [0] staged host inputs, the per-changeset and per-change columns, class_off
     // and rocPRIM temp, [1] the per-match columns, the slot table and the sort's temp, [2] staged host outputs
     corro::DevBuf d_match[3];
+    // the bookie's image (bookie_image.hip): [0] keys, permutations, flags, scans and rocPRIM temp, [1] staged
+    // host inputs, [2] the pieces, the segment list and staged host rows and outputs
+    corro::DevBuf d_bookimg[3];
     corro::DevBuf d_match_base;   // u32 per table (+ 1): its first column slot
     bool match_base_ready = false;
     bool wire_schema_ready = false;

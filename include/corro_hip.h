@@ -1334,6 +1334,79 @@ typedef struct {
 int corro_assemble_answers_buffered(corro_ctx *ctx, const corro_assemble_buffered_in *in, int mem, corro_assembled *out,
                                     int pass);
 
+/* ------------------------------------------------------------------ the bookie's image: save and restore */
+
+/* The bookie as the reference keeps it across a restart: the three bookkeeping tables plus the per-actor
+ * crsql_db_versions value. corro_bookie_save writes the image (the caller puts it into its durable
+ * store in the transaction that commits the merge); corro_bookie_load is BookedVersions::from_conn
+ * (corro-types/src/agent.rs:1282-1351) for every actor plus the startup loop that calls it
+ * (corro-agent/src/agent/run_root.rs:139-201). The books are host arrays; the __corro_buffered_changes
+ * rows lie where `mem` says (CORRO_MEM_HOST or CORRO_MEM_DEVICE), and with CORRO_MEM_DEVICE the rows
+ * of the device row pool never visit the host, in either direction.
+ *
+ *   actors      nactors ids of 16 bytes; max = the crsql_db_versions value, -1 for None.
+ *   gap_*       CSR over the actors: the __corro_bookkeeping_gaps rows (start, end).
+ *   seq_*       CSR over the actors: the __corro_seq_bookkeeping rows, one per stored seq range
+ *               (version, start_seq, end_seq, last_seq, ts).
+ *   site_ids    nsites ids of 16 bytes: entry s is the id behind site ordinal s (crsql_site_id), for
+ *               every ordinal the rows use and every actor that has seq rows (the bookie keys both
+ *               tables by ordinal). An ordinal nothing uses holds sixteen zero bytes.
+ *   rows        the __corro_buffered_changes rows: rows.n of them, every corro_changes array but
+ *               val_off / val_size / val_data, which are there only with rows.val_data_len > 0 (some
+ *               row holds a long value); val_data lies in `mem` like the rest.
+ *
+ * corro_bookie_save. Two passes: pass 0 sets nactors, ngaps, nseqrows, nsites, rows.n,
+ * rows.val_data_len and stamp (a digest of the books and of where the rows lie); the caller allocates
+ * (gap_off and seq_off hold nactors + 1 entries); pass 1 fills. A bookie that changed in between --
+ * its counts or its stamp differ -- gives CORRO_E_INVALID and nothing is written. Actors come in
+ * ActorId byte order and max is last(); an actor's gaps ascend; its seq rows ascend by (version,
+ * start_seq). Rows come sorted by (site, db_version, seq): the rows the bookie holds in its device pool
+ * are gathered from their segments by a kernel driven from the output, the rows it holds on the host
+ * (versions that are not canonical, long values) are merged into the same order. ctx may be NULL when
+ * the bookie holds no pool row and mem is CORRO_MEM_HOST (then no device is touched); a pool on another
+ * device than ctx's is CORRO_E_INVALID. Save changes nothing in the bookie or the pool: no key is
+ * materialised and no pool row moves, so it invalidates no offset of corro_bookie_buffered_index and
+ * no other call's result. ready versions (corro_bookie_take_ready) are not part of the image: load
+ * derives them.
+ *
+ * corro_bookie_load loads into an empty bookie (one that holds an actor: CORRO_E_INVALID). Per actor,
+ * in the order given (any order; a repeated id is CORRO_E_INVALID), it is from_conn, quirks included:
+ * max starts as given; every seq row goes through insert_partial in the order given (agent.rs:1414-1432:
+ * the first row of a version fixes its last_seq and ts and raises max to the version, later rows only
+ * extend its seqs); the gaps are inserted as given and coalesce as RangeInclusiveSet does; a gap above
+ * max is kept and does not move max (agent.rs:1338-1342). Every loaded partial whose seqs leave no gap
+ * over 0 ..= last_seq is listed by corro_bookie_take_ready, actors in the image's order, versions
+ * ascending (run_root.rs:181-193; 0 ..=, not is_complete's 1 ..=). An actor with seq rows that is not
+ * in site_ids is CORRO_E_INVALID.
+ * The rows may come in any order. On the device they are keyed by (site, db_version, seq), sorted,
+ * checked (a duplicate key is CORRO_E_INVALID: the table's primary key), cut into segments -- maximal
+ * runs of consecutive seqs inside one (site, db_version) -- and gathered into the bookie's row pool in
+ * sorted order; the host receives the segment list alone. A (site, db_version) holding a row the pool
+ * cannot represent (a long value, a seq of 2^32 - 1) keeps all its rows on the host, as
+ * corro_process_multiple_changes would have stored them. A negative db_version, a site ordinal at or
+ * above nsites, one not registered in ctx, or registered there to another id than site_ids says, is
+ * CORRO_E_INVALID; 2^32 rows or more CORRO_E_RANGE. With rows.n == 0 ctx may be NULL and no device is
+ * touched.
+ * Failure atomicity: any failure leaves the bookie empty as corro_bookie_new made it, its pool
+ * released, and ctx as it was (load never writes the merged state, so it never poisons ctx).
+ * CORRO_FAULT=bufpool_reserve fails load's pool reservation. */
+typedef struct {
+    uint64_t nactors, ngaps, nseqrows;     /* save: pass 0 outputs, pass 1 inputs; load: inputs */
+    uint32_t nsites;
+    uint64_t stamp;                        /* save: pass 0 output, pass 1 input; load: ignored */
+    uint8_t *actor_ids;                    /* 16 * nactors */
+    int64_t *max;                          /* nactors: -1 = None */
+    uint64_t *gap_off;                     /* nactors + 1 */
+    uint64_t *gap_start, *gap_end;         /* ngaps */
+    uint64_t *seq_off;                     /* nactors + 1 */
+    uint64_t *seq_version, *seq_start, *seq_end, *seq_last, *seq_ts;   /* nseqrows */
+    uint8_t *site_ids;                     /* 16 * nsites */
+    corro_changes rows;                    /* in `mem`; save writes through its pointers */
+} corro_bookie_image;
+
+int corro_bookie_save(corro_ctx *ctx, corro_bookie *bk, corro_bookie_image *img, int mem, int pass);
+int corro_bookie_load(corro_ctx *ctx, corro_bookie *bk, const corro_bookie_image *img, int mem);
+
 /* ------------------------------------------------------------------ match_changes */
 
 /* match_changes (corro-types/src/updates.rs:420-481) for the subscriptions and the update handles,
