@@ -47,12 +47,15 @@ EXPORTS = [
     "corro_bookie_buffered_index", "corro_buffered_spans", "corro_assemble_answers_buffered",
     "corro_decode_states", "corro_bookie_sync_book", "corro_encode_states", "corro_match_changes",
     "corro_bookie_save", "corro_bookie_load",
+    "corro_pk_find", "corro_pk_find_device", "corro_read_rows",
 ]
 
 CORRO_CS_FULL, CORRO_CS_EMPTY, CORRO_CS_EMPTY_SET = 0, 1, 2
 KNOWN = {0: "skipped", 1: "current", 2: "cleared", 3: "partial"}
 CORRO_TCID_UNKNOWN = 0xFFFFFFFF
 CORRO_VAL_LONG = 255  # val_len of a TEXT/BLOB value longer than 16 bytes
+CORRO_PK_ABSENT = 0xFFFFFFFFFFFFFFFF  # corro_pk_find: a key the intern table does not hold
+CORRO_READ_VALUES = 1  # corro_read_in.flags: attach long values' bytes
 
 
 class CorroError(RuntimeError):
@@ -303,6 +306,16 @@ class MatchOut(C.Structure):
         "class_off", "cand_change", "cand_cs", "cand_table", "cand_pk", "cand_cl")]
 
 
+class ReadIn(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("table", C.c_void_p), ("pk", C.c_void_p), ("flags", C.c_uint32)]
+
+
+class ReadOut(C.Structure):
+    _fields_ = [("nrows", C.c_uint64), ("val_data_len", C.c_uint64), ("status", C.c_void_p), ("cl", C.c_void_p),
+                ("row_off", C.c_void_p), ("rows", Rows), ("val_off", C.c_void_p), ("val_size", C.c_void_p),
+                ("val_data", C.c_void_p)]
+
+
 _lib = None
 
 
@@ -423,6 +436,9 @@ def lib():
         "corro_pk_keys": (i32, [vp, u32, vp, vp, u64, vp]),
         "corro_pk_keys_device": (i32, [vp, u32, vp, vp, u64, vp]),
         "corro_pk_bytes": (i32, [vp, u32, vp, u64, vp, u64, vp]),
+        "corro_pk_find": (i32, [vp, u32, vp, vp, u64, vp]),
+        "corro_pk_find_device": (i32, [vp, u32, vp, vp, u64, vp]),
+        "corro_read_rows": (i32, [vp, C.POINTER(ReadIn), i32, C.POINTER(ReadOut), i32]),
         "corro_pk_canonical": (i32, [C.c_char_p, u64, vp, u64, vp]),
     }
     for name, (res, args) in sig.items():

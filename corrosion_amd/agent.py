@@ -384,6 +384,14 @@ class Agent:
         return updates.match_changes(self.engine, dec["changes"], processed.impact, dec["cs_dev"], filters, device=True,
                                      ncs=dec["n_dev"])
 
+    def read_matched(self, processed, dec, filters, values=True):
+        """match_changes, then the candidates' current rows (updates.read_candidates) where they lie: returns
+        (match result, read_rows result), candidate j of the first owning rows [row_off[j], row_off[j + 1])
+        of the second."""
+        from . import updates
+        res = self.match_changes(processed, dec, filters)
+        return res, updates.read_candidates(self.engine, res, values=values)
+
     def take_ready(self):
         return self.bookie.take_ready()
 

@@ -134,8 +134,10 @@ struct PkRefs {
     const uint32_t *tcid = nullptr;  // null: every change is of `table`
     uint64_t limit = ~0ULL;          // bytes readable from base: a reference past it is a bad pk
 };
+// find_only (corro_pk_find): nothing is claimed or committed -- a key the table does not hold gets
+// CORRO_PK_ABSENT and the table stays as it was.
 int pk_keys_device(corro_ctx *ctx, uint32_t table, const PkRefs &r, uint64_t n, uint64_t *keys, uint8_t *bad,
-                   uint64_t *nbad);
+                   uint64_t *nbad, bool find_only = false);
 bool pk_canonical(const uint8_t *p, uint64_t len, std::string &out, bool *single_int, int64_t *ival);
 std::string pack_int_pk(int64_t v);
 
@@ -309,6 +311,9 @@ struct corro_ctx {
     // the bookie's image (bookie_image.hip): [0] keys, permutations, flags, scans and rocPRIM temp, [1] staged
     // host inputs, [2] the pieces, the segment list and staged host rows and outputs
     corro::DevBuf d_bookimg[3];
+    // row reads (row_read.hip): [0] staged host keys, the per-key columns, row_off and rocPRIM temp, [1] the
+    // per-row value offsets and staged host rows
+    corro::DevBuf d_read[2];
     corro::DevBuf d_match_base;   // u32 per table (+ 1): its first column slot
     bool match_base_ready = false;
     bool wire_schema_ready = false;

@@ -29,6 +29,8 @@
 // table holds (load <= 1/2 with a share of new ones), not by the changes of a call; a probe that runs
 // past PK_MAX_PROBE slots marks the call for a retry with a table four times larger (rebuilt from the
 // arena). Any failed call drops its claims (the slots rebuilt from the committed keys).
+// corro_pk_find runs k_pk_find (and the slow pair) as a lookup (FIND): an empty slot ends a probe with
+// CORRO_PK_ABSENT, nothing is claimed, and the call ends before k_pk_mark.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -522,6 +524,11 @@ constexpr uint32_t PK_FIND_THREADS = 256;
 // compare against the claimant's input bytes (read-only: a claimant here always has canonical input),
 // take keys[i] = PENDING | claimant and raise the claim's first-seen word. Inputs that are not
 // canonical are listed for the slow path (canonicalised into a scratch, then probed).
+// FIND (corro_pk_find): the same parse and probe, read-only -- the first empty slot of a key's probe path
+// ends the probe (keys are never removed from the table, so a held key lies before it) and the key is
+// CORRO_PK_ABSENT; nothing is claimed, listed as a claim or counted. The probe then runs to that slot
+// however far it is: a find cannot ask for a larger table.
+template <bool FIND>
 __global__ void __launch_bounds__(PK_FIND_THREADS) k_pk_find(PkArgs a) {
     __shared__ __attribute__((aligned(16))) uint8_t s_st[PK_FIND_THREADS / 64][PK_WAVE_STAGE];
     const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -614,7 +621,8 @@ __global__ void __launch_bounds__(PK_FIND_THREADS) k_pk_find(PkArgs a) {
                     if (true) continue;
 #endif
                     uint64_t res = ~0ULL;
-                    for (uint32_t step = 0; step < PK_MAX_PROBE; step++, sl = pk_next(sl, a.nsl)) {
+                    const uint64_t max_probe = FIND ? a.nsl : PK_MAX_PROBE;   // (FIND with no table yet: 0)
+                    for (uint64_t step = 0; step < max_probe; step++, sl = pk_next(sl, a.nsl)) {
                         PkSlot *ps = a.slots + sl;
                         unsigned long long w;
                         PkWords q;
@@ -624,6 +632,7 @@ __global__ void __launch_bounds__(PK_FIND_THREADS) k_pk_find(PkArgs a) {
 #if !(PK_DIAG & 128)
                         if (w == 0) w = __hip_atomic_load(&ps->w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #endif
+                        if (FIND && w == 0) break;
                         if (w == 0) {
                             const unsigned long long want = ((unsigned long long)tag << 32) | (PK_NEW | (uint32_t)i);
                             w = atomicCAS(&ps->w, 0ULL, want);
@@ -654,9 +663,9 @@ __global__ void __launch_bounds__(PK_FIND_THREADS) k_pk_find(PkArgs a) {
                             break;
                         }
                     }
-                    if (res == ~0ULL) {
+                    if (res == ~0ULL && !FIND) {
                         atomicOr(&a.ctl[3], 1ULL);  // (the table is too full: the call retries)
-                    } else {
+                    } else {   // (FIND: ~0 is CORRO_PK_ABSENT)
 #if PK_DIAG & 16
                         __builtin_nontemporal_store(res, &a.keys[i]);
 #else
@@ -709,6 +718,7 @@ __global__ void __launch_bounds__(256) k_pk_canon(PkArgs a, uint64_t nslow) {
 
 // (slow path) the listed changes probe the table; every claimant's canonical bytes, length and hash were
 // written by an earlier kernel, so a claim is compared through cref / clen / h
+template <bool FIND>
 __global__ void __launch_bounds__(256) k_pk_probe_slow(PkArgs a, uint64_t nslow) {
     const uint32_t lane = threadIdx.x & 63;
     (void)lane;
@@ -727,12 +737,14 @@ __global__ void __launch_bounds__(256) k_pk_probe_slow(PkArgs a, uint64_t nslow)
             if (cl <= PK_INLINE) mw = pk_words(mine, cl);
             sl = pk_slot_of(h, a.nhome);
             uint64_t res = ~0ULL;
-            for (uint32_t step = 0; step < PK_MAX_PROBE; step++, sl = pk_next(sl, a.nsl)) {
+            const uint64_t max_probe = FIND ? a.nsl : PK_MAX_PROBE;
+            for (uint64_t step = 0; step < max_probe; step++, sl = pk_next(sl, a.nsl)) {
                 PkSlot *ps = a.slots + sl;
                 unsigned long long w;
                 PkWords q;
                 pk_slot_read(ps, w, q);
                 if (w == 0) w = __hip_atomic_load(&ps->w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (FIND && w == 0) break;
                 if (w == 0) {
                     w = atomicCAS(&ps->w, 0ULL, ((unsigned long long)tag << 32) | (PK_NEW | i));
                     if (w == 0) {
@@ -759,7 +771,7 @@ __global__ void __launch_bounds__(256) k_pk_probe_slow(PkArgs a, uint64_t nslow)
                     break;
                 }
             }
-            if (res == ~0ULL)
+            if (res == ~0ULL && !FIND)
                 atomicOr(&a.ctl[3], 1ULL);
             else
                 a.keys[i] = res;
@@ -993,7 +1005,7 @@ void pk_drop_claims(corro_ctx *ctx, PkTable &t) {
 }  // namespace
 
 int pk_keys_device(corro_ctx *ctx, uint32_t table, const PkRefs &r, uint64_t n, uint64_t *keys, uint8_t *bad,
-                   uint64_t *nbad) {
+                   uint64_t *nbad, bool find_only) {
     if (nbad) *nbad = 0;
     if (n == 0) return CORRO_OK;
     if (table >= ctx->tables.size()) return fail(CORRO_E_UNKNOWN_TABLE, "no such table index");
@@ -1046,7 +1058,13 @@ int pk_keys_device(corro_ctx *ctx, uint32_t table, const PkRefs &r, uint64_t n, 
         // sixty-fourth into one that holds keys.)
         const uint64_t est_new = std::max<uint64_t>(t.n ? n / 64 : n / 16, 1ULL << 16);
         const uint64_t want = t.n + est_new;
-        if (t.nslots < pk_slots_for(want, 3, 4)) CORRO_TRY(pk_slots_resize(ctx, t, want));
+        if (find_only) {
+            // (the slots are an index over the committed keys: a table that holds keys but lost its slots to
+            // a failed call gets them back; one that holds no key is probed not at all)
+            if (t.n && !t.nslots) CORRO_TRY(pk_slots_resize(ctx, t, t.n));
+        } else if (t.nslots < pk_slots_for(want, 3, 4)) {
+            CORRO_TRY(pk_slots_resize(ctx, t, want));
+        }
         a.koff = t.d_off.as<uint64_t>();
         a.kbytes = t.d_bytes.as<uint8_t>();
         a.khash = t.d_hash.as<uint64_t>();
@@ -1055,7 +1073,7 @@ int pk_keys_device(corro_ctx *ctx, uint32_t table, const PkRefs &r, uint64_t n, 
     }
     // from the first probe on, an error return drops this call's claims from the slots
     auto failc = [&](int rc) {
-        if (t.interned && t.nslots) pk_drop_claims(ctx, t);
+        if (t.interned && t.nslots && !find_only) pk_drop_claims(ctx, t);   // (a find claims nothing)
         return rc;
     };
 #define TRY_PKC(x)                            \
@@ -1072,14 +1090,14 @@ int pk_keys_device(corro_ctx *ctx, uint32_t table, const PkRefs &r, uint64_t n, 
     DevBuf scratch;  // (non-canonical inputs: their canonical bytes)
     for (int attempt = 0;; attempt++) {
         a.slots = t.d_slots.as<PkSlot>();
-        a.nsl = t.nslots + PK_PAD;
+        a.nsl = t.nslots ? t.nslots + PK_PAD : 0;   // (no slots: only a find of an empty table)
         a.nhome = t.nslots;
         HIP_PKC(hipMemsetAsync(a.ctl, 0, 64, s));
         if (bad) HIP_PKC(hipMemsetAsync(bad, 0, n, s));
         const uint32_t nwaves = (uint32_t)((n + 63) / 64);
         const uint32_t grid = std::max<uint32_t>(1, std::min<uint32_t>((nwaves + 3) / 4, PK_GRID_MAX));
         if (fault_armed("pk_find")) return failc(fail(CORRO_E_DEVICE, "injected fault (CORRO_FAULT): pk_find"));
-        hipLaunchKernelGGL(k_pk_find, dim3(grid), dim3(PK_FIND_THREADS), 0, s, a);
+        hipLaunchKernelGGL(find_only ? k_pk_find<true> : k_pk_find<false>, dim3(grid), dim3(PK_FIND_THREADS), 0, s, a);
         HIP_PKC(hipGetLastError());
         HIP_PKC(hipMemcpyAsync(ctl, a.ctl, 64, hipMemcpyDeviceToHost, s));
         HIP_PKC(hipStreamSynchronize(s));
@@ -1092,12 +1110,13 @@ int pk_keys_device(corro_ctx *ctx, uint32_t table, const PkRefs &r, uint64_t n, 
                                                               "it interned"));
         }
         if (!t.interned) return CORRO_OK;
-        t.max_len = std::max<uint64_t>(t.max_len, ctl[1]);
+        if (!find_only) t.max_len = std::max<uint64_t>(t.max_len, ctl[1]);
         if (ctl[2] && !ctl[3]) {  // slow path: non-canonical inputs canonicalised, then probed
             HIP_PKC((scratch.ensure(std::max<uint64_t>(ctl[5], 1)) == CORRO_OK) ? hipSuccess : hipErrorOutOfMemory);
             a.scratch = scratch.as<uint8_t>();
             hipLaunchKernelGGL(k_pk_canon, pk_grid(ctl[2]), dim3(256), 0, s, a, (uint64_t)ctl[2]);
-            hipLaunchKernelGGL(k_pk_probe_slow, pk_grid(ctl[2]), dim3(256), 0, s, a, (uint64_t)ctl[2]);
+            hipLaunchKernelGGL(find_only ? k_pk_probe_slow<true> : k_pk_probe_slow<false>, pk_grid(ctl[2]), dim3(256), 0, s,
+                               a, (uint64_t)ctl[2]);
             HIP_PKC(hipGetLastError());
             HIP_PKC(hipMemcpyAsync(ctl + 3, a.ctl + 3, 16, hipMemcpyDeviceToHost, s));
             HIP_PKC(hipStreamSynchronize(s));
@@ -1107,6 +1126,7 @@ int pk_keys_device(corro_ctx *ctx, uint32_t table, const PkRefs &r, uint64_t n, 
         if (attempt == 6) return failc(fail(CORRO_E_DEVICE, "internal: interned pk probes do not terminate"));
         TRY_PKC(pk_slots_resize(ctx, t, t.n, 4 * t.nslots));
     }
+    if (find_only) return CORRO_OK;  // (stopped before k_pk_mark / k_pk_newkeys / k_pk_commit: nothing was claimed)
     const uint64_t nclaims = ctl[4];
     if (!nclaims) return CORRO_OK;  // (a warm call: every key held, ids already in keys[])
     HIP_PKC(hipMemsetAsync(a.newf, 0, 4 * n, s));
@@ -1181,9 +1201,10 @@ int corro_table_set_pk_interned(corro_ctx *ctx, uint32_t table, int interned) {
     return CORRO_OK;
 }
 
-// host pks: staged into HBM and interned there (the one intern table, pk_keys_device)
-int corro_pk_keys(corro_ctx *ctx, uint32_t table, const uint8_t *bytes, const uint64_t *off, uint64_t n,
-                  uint64_t *keys) {
+// host pks: staged into HBM and interned (or, find_only, looked up) there (the one intern table,
+// pk_keys_device)
+static int pk_keys_host(corro_ctx *ctx, uint32_t table, const uint8_t *bytes, const uint64_t *off, uint64_t n,
+                        uint64_t *keys, bool find_only) {
     if (!ctx || (n && (!bytes || !off || !keys))) return fail(CORRO_E_INVALID, "NULL argument");
     if (table >= ctx->tables.size()) return fail(CORRO_E_UNKNOWN_TABLE, "no such table index");
     if (n == 0) return CORRO_OK;
@@ -1205,9 +1226,28 @@ int corro_pk_keys(corro_ctx *ctx, uint32_t table, const uint8_t *bytes, const ui
     r.base = dbytes;
     r.off = doff;
     r.limit = nb;
-    if (int rc = pk_keys_device(ctx, table, r, n, dkeys, nullptr, nullptr)) return rc;
+    if (int rc = pk_keys_device(ctx, table, r, n, dkeys, nullptr, nullptr, find_only)) return rc;
     CORRO_HIP_TRY(hipMemcpy(keys, dkeys, n * 8, hipMemcpyDeviceToHost));
     return CORRO_OK;
+}
+
+int corro_pk_keys(corro_ctx *ctx, uint32_t table, const uint8_t *bytes, const uint64_t *off, uint64_t n,
+                  uint64_t *keys) {
+    return pk_keys_host(ctx, table, bytes, off, n, keys, false);
+}
+
+int corro_pk_find(corro_ctx *ctx, uint32_t table, const uint8_t *bytes, const uint64_t *off, uint64_t n,
+                  uint64_t *keys) {
+    return pk_keys_host(ctx, table, bytes, off, n, keys, true);
+}
+
+int corro_pk_find_device(corro_ctx *ctx, uint32_t table, const uint8_t *bytes, const uint64_t *off, uint64_t n,
+                         uint64_t *keys) {
+    if (!ctx || (n && (!bytes || !off || !keys))) return fail(CORRO_E_INVALID, "NULL argument");
+    PkRefs r;
+    r.base = bytes;
+    r.off = off;
+    return pk_keys_device(ctx, table, r, n, keys, nullptr, nullptr, true);
 }
 
 int corro_pk_keys_device(corro_ctx *ctx, uint32_t table, const uint8_t *bytes, const uint64_t *off, uint64_t n,

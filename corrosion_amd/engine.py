@@ -47,6 +47,28 @@ _REQDEC_OUT = (("pair_actor", np.uint8, "npairs", 16, 0), ("pair_site", np.uint3
                ("ent_need", np.uint64, "nents"))
 
 
+# corro_read_out: the per-key arrays of pass 0, the per-row arrays of pass 1
+_READ_PRE = (("status", np.uint8, "n"), ("cl", np.int64, "n"), ("row_off", np.uint64, "n", 1, 1))
+_READ_ROWS = tuple(("rows." + k, dt, "nrows") for k, dt in ROW_FIELDS.items())
+_READ_LONG = (("val_off", np.uint64, "nrows"), ("val_size", np.uint32, "nrows"), ("val_data", np.uint8, "val_data_len"))
+
+
+def rows_as_batch(rows):
+    """The rows of a read_rows(values=True) result as a batch apply() takes, in the same memory. Every
+    array is passed as it is but cl: corro_rows carries it as int64, corro_changes as uint32."""
+    cl = rows["cl"]
+    if _is_torch(cl):
+        import torch
+        cl = cl.to(torch.int32)
+    else:
+        cl = np.asarray(cl).astype(np.uint32)
+    batch = {k: rows[k] for k in FIXED_FIELDS if k != "cl"}
+    batch["cl"] = cl
+    if "val_data" in rows and Mem.of(rows["val_data"]).count(rows["val_data"]):
+        batch.update({k: rows[k] for k in LONG_FIELDS + ("val_data",)})
+    return batch
+
+
 class MergeEngine:
     def __init__(self, schema, capacity_hint=1 << 20, device=0, interned=()):
         """schema: {table_name: [column names]} in table order (cid k = column k-1, cid 0 = '-1').
@@ -175,6 +197,28 @@ class MergeEngine:
         L.check(L.lib().corro_pk_keys_device(self._h, t, data.data_ptr(), off.data_ptr(), n, keys.data_ptr()))
         return keys[:n]
 
+    def pk_find(self, table, packed):
+        """pk_keys that only looks (corro_pk_find): the row keys of packed pks, L.CORRO_PK_ABSENT for a
+        key an interned table does not hold; the intern table is left as it was. packed: a list of bytes
+        (a numpy array of keys comes back), or (data, off) CUDA tensors as pk_keys_device takes them
+        (corro_pk_find_device; an int64 CUDA tensor comes back, CORRO_PK_ABSENT reading -1)."""
+        t = self.table_index(table)
+        if isinstance(packed, tuple):
+            import torch
+            data, off = packed
+            n = int(off.numel()) - 1
+            keys = torch.empty(max(n, 1), dtype=torch.int64, device=off.device)
+            torch.cuda.current_stream().synchronize()
+            L.check(L.lib().corro_pk_find_device(self._h, t, data.data_ptr(), off.data_ptr(), n, keys.data_ptr()))
+            return keys[:n]
+        lens = np.array([len(b) for b in packed], np.uint64)
+        off = np.zeros(len(packed) + 1, np.uint64)
+        off[1:] = np.cumsum(lens)
+        buf = np.frombuffer(b"".join(bytes(b) for b in packed) or b"\0", np.uint8)
+        keys = np.zeros(max(1, len(packed)), np.uint64)
+        L.check(L.lib().corro_pk_find(self._h, t, buf.ctypes.data, off.ctypes.data, len(packed), keys.ctypes.data))
+        return keys[:len(packed)]
+
     def pk_bytes(self, table, keys):
         """Canonical packed pk bytes of row keys of one table."""
         t = self.table_index(table)
@@ -285,6 +329,35 @@ class MergeEngine:
         rows = {k: a[: w.value] for k, a in out.items()}
         rows["long_values"] = self.long_values(rows)
         return rows
+
+    def read_rows(self, tables, pks, values=True, flags=None):
+        """The current rows of the keys (tables[i], pks[i]) in request order (corro_read_rows): table
+        indices and row keys as numpy arrays (host results) or CUDA tensors (device results; only totals
+        reach the host) -- a match_changes result's "cand_table" / "cand_pk" as they are. Returns "status"
+        (0 absent, 1 live, 2 deleted), "key_cl" (corro_read_out.cl) and "row_off" (n + 1) per key, the
+        crsql_changes columns of export() per row -- key i owns rows [row_off[i], row_off[i + 1]), sentinel first, then by cid --
+        "nrows", and with values the long values' "val_off" / "val_size" / "val_data" and "val_data_len"
+        (rows_as_batch turns such a result into a batch for another engine). Host results also carry
+        "long_values" like export(). flags overrides the flag word (tests)."""
+        mem = Mem.of(pks)
+        s = L.ReadIn()
+        n = mem.count(pks)
+        s.n = n
+        s.flags = (L.CORRO_READ_VALUES if values else 0) if flags is None else flags
+        keep = mem.fill(s, {"table": tables, "pk": pks}, (("table", np.uint32, n), ("pk", np.uint64, n)))
+        post = _READ_ROWS + (_READ_LONG if s.flags & L.CORRO_READ_VALUES else ())
+        res = two_pass(L.lib().corro_read_rows, (self._h, C.byref(s), mem.const), mem, L.ReadOut(),
+                       tuple((k, dt, n, *me) for k, dt, _n, *me in _READ_PRE), ("nrows", "val_data_len"), post)
+        del keep
+        res["key_cl"] = res.pop("cl")      # (the rows' own "cl" column keeps the name, as in export())
+        res = {(k[5:] if k.startswith("rows.") else k): a for k, a in res.items()}
+        if not mem.on_dev:
+            if "val_data" in res:
+                raw, off, size = res["val_data"].tobytes(), res["val_off"], res["val_size"]
+                res["long_values"] = {int(i): raw[int(off[i]):int(off[i]) + int(size[i])] for i in np.nonzero(size)[0]}
+            else:
+                res["long_values"] = self.long_values(res)
+        return res
 
     def track_touched(self, on=True):
         """List the rows every apply addresses, for export_touched (corro_ctx_track_touched)."""

@@ -153,6 +153,14 @@ def match_changes(engine, changes, impactful, cs, filters, device=None, ncs=None
     return {**tp.result(), **tot}
 
 
+def read_candidates(engine, result, values=True):
+    """The current rows of a match_changes result's candidates (MergeEngine.read_rows of its "cand_table" /
+    "cand_pk"), what handle_candidates (updates.rs:270-305) and the subscription matcher read next: key j
+    is candidate j, so "status", "key_cl" and "row_off" line up with the candidate columns. The rows stay on the
+    device when the result is there."""
+    return engine.read_rows(result["cand_table"], result["cand_pk"], values=values)
+
+
 def _host(a, dt):
     if _is_torch(a):
         a = a.cpu().numpy()

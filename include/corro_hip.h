@@ -180,6 +180,17 @@ int corro_pk_keys(corro_ctx *ctx, uint32_t table, const uint8_t *bytes, const ui
  * call's new keys, in no particular order). Synchronous. */
 int corro_pk_keys_device(corro_ctx *ctx, uint32_t table, const uint8_t *bytes, const uint64_t *off, uint64_t n,
                          uint64_t *keys);
+/* corro_pk_keys / corro_pk_keys_device that only look: a read must not grow the intern table. Arguments,
+ * canonicalisation and error codes are theirs (a non-canonical encoding finds its canonical key, a
+ * malformed one is CORRO_E_INVALID); a key the table does not hold yields CORRO_PK_ABSENT, and the table,
+ * its size and its next id stay exactly as they were. A table keyed by its INTEGER pk returns the integer,
+ * as corro_pk_keys does. The probe is the one corro_pk_keys_device runs, stopped at the first empty slot
+ * instead of claiming it. */
+#define CORRO_PK_ABSENT UINT64_MAX
+int corro_pk_find(corro_ctx *ctx, uint32_t table, const uint8_t *bytes, const uint64_t *off, uint64_t n,
+                  uint64_t *keys);
+int corro_pk_find_device(corro_ctx *ctx, uint32_t table, const uint8_t *bytes, const uint64_t *off, uint64_t n,
+                         uint64_t *keys);
 /* Row keys of `table` -> canonical packed pk bytes (export, extraction): key i's bytes at
  * [out_off[i], out_off[i+1]); out_off holds n + 1 entries; CORRO_E_RANGE if cap < out_off[n]. */
 int corro_pk_bytes(corro_ctx *ctx, uint32_t table, const uint64_t *keys, uint64_t n, uint8_t *bytes, uint64_t cap,
@@ -1476,6 +1487,61 @@ typedef struct {
 } corro_match_out;
 
 int corro_match_changes(corro_ctx *ctx, const corro_match_in *in, int mem, corro_match_out *out, int pass);
+
+/* ------------------------------------------------------------------ read rows by primary key */
+
+/* SELECT ... WHERE (table, pk) IN (...) over the merged state: what handle_candidates
+ * (corro-types/src/updates.rs:270-305) and the subscription matcher (pubsub.rs) ask for every candidate of
+ * corro_match_changes, whose cand_table / cand_pk columns are this call's input as they lie; also a
+ * caller's read of a replicated row by its key, and the row-granular repair of one replica from another.
+ *
+ * Key i owns rows [row_off[i], row_off[i + 1]): the row's complete current clock set in crsql_changes
+ * form, the sentinel first when present, then the cells by ascending cid; every field is what
+ * corro_state_export gives for that record (cl = the row's causal length: the sentinel's col_version if
+ * the row has a sentinel clock, else 1; ts; site ordinals; the stored, affinity-converted value). status
+ * is 1 for an odd causal length, 2 for an even one (the row then has its sentinel alone) and 0 for an
+ * absent row -- a table index the schema does not have, a pk that was never merged, CORRO_PK_ABSENT for
+ * an interned table (its ids lie below 2^31, so no case is made of it) -- which owns no rows, has cl 0 and
+ * never makes the call fail. Output order is request order; a key listed k times is answered k times.
+ * The read writes nothing into the store, the value arena or the intern table.
+ *
+ * Long values: val1 carries the arena handle, as in exports. With CORRO_READ_VALUES every row whose
+ * val_len is CORRO_VAL_LONG also has its bytes at val_data[val_off[k], val_off[k] + val_size[k]); other
+ * rows have val_size 0. rows + val_off / val_size / val_data are then the arrays corro_changes takes, in
+ * `mem`'s memory, for corro_apply_batch of another context with the same schema and site registration.
+ * One field is not the identity: corro_rows.cl is int64 and corro_changes.cl is uint32, so the caller
+ * narrows that column (a causal length is below 2^32); a long row's val1 handle is not read by an apply
+ * and differs in the receiving context, its bytes do not.
+ *
+ * Two passes: pass 0 fills status, cl, row_off, nrows and val_data_len (0 without the flag); pass 1
+ * computes them again and fills the rest; NULL arrays of `rows` are not written. `mem` (CORRO_MEM_HOST or
+ * CORRO_MEM_DEVICE) covers every array of both structs: with device memory only the two totals cross
+ * PCIe, with host memory the keys go up and the results come down in one copy per array. Synchronous on
+ * the context's stream. Fails, before anything is written, with CORRO_E_INVALID for a NULL struct, a bad
+ * mem or pass, unknown flag bits, a required array that is NULL while its count is not 0, or a pass-1
+ * nrows / val_data_len that differs from what pass 1 computes; with CORRO_E_RANGE for n >= 2^31 or
+ * nrows >= 2^32; with CORRO_E_DEVICE for a poisoned context, as corro_state_export. n == 0 gives
+ * nrows = 0 and row_off[0] = 0; an empty state answers every key with status 0. */
+#define CORRO_READ_VALUES 1u
+typedef struct {
+    uint64_t n;
+    const uint32_t *table;                 /* n: table index (table_cid >> 16), e.g. corro_match_out.cand_table */
+    const uint64_t *pk;                    /* n: row key as in corro_changes.pk, e.g. corro_match_out.cand_pk */
+    uint32_t flags;                        /* CORRO_READ_VALUES: attach long values' bytes */
+} corro_read_in;
+
+typedef struct {
+    uint64_t nrows, val_data_len;          /* pass 0 outputs, pass 1 inputs */
+    uint8_t *status;                       /* n (pass 0): 0 absent, 1 live, 2 deleted */
+    int64_t *cl;                           /* n (pass 0): the row's causal length, 0 if absent */
+    uint64_t *row_off;                     /* n + 1 (pass 0) */
+    corro_rows rows;                       /* nrows each (pass 1); NULL arrays are not written */
+    uint64_t *val_off;                     /* nrows (pass 1, CORRO_READ_VALUES) */
+    uint32_t *val_size;                    /* nrows */
+    uint8_t *val_data;                     /* val_data_len */
+} corro_read_out;
+
+int corro_read_rows(corro_ctx *ctx, const corro_read_in *in, int mem, corro_read_out *out, int pass);
 
 #ifdef __cplusplus
 }
