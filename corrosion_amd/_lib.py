@@ -48,6 +48,7 @@ EXPORTS = [
     "corro_decode_states", "corro_bookie_sync_book", "corro_encode_states", "corro_match_changes",
     "corro_bookie_save", "corro_bookie_load",
     "corro_pk_find", "corro_pk_find_device", "corro_read_rows",
+    "corro_process_fully_buffered_batch",
 ]
 
 CORRO_CS_FULL, CORRO_CS_EMPTY, CORRO_CS_EMPTY_SET = 0, 1, 2
@@ -410,6 +411,7 @@ def lib():
         "corro_process_multiple_changes": (i32, [vp, vp, vp, u64, C.POINTER(Changes), i32, C.POINTER(ProcessOut)]),
         "corro_bookie_take_ready": (i32, [vp, vp, vp, u64, vp]),
         "corro_process_fully_buffered": (i32, [vp, vp, vp, u64, vp]),
+        "corro_process_fully_buffered_batch": (i32, [vp, vp, vp, vp, u64, vp]),
         "corro_bookie_last": (i32, [vp, vp, vp]),
         "corro_bookie_needed": (i32, [vp, vp, vp, vp, u64, vp]),
         "corro_bookie_contains_all": (i32, [vp, vp, u64, u64, i32, u64, u64, vp]),

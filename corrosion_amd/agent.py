@@ -188,6 +188,22 @@ class Bookie:
         L.check(L.lib().corro_bookie_take_ready(self._h, a.ctypes.data, v.ctypes.data, c.value, C.byref(c)))
         return [(bytes(a[k]), int(v[k])) for k in range(c.value)]
 
+    def process_ready(self, engine, pairs):
+        """process_fully_buffered_changes of the (actor, version) pairs in list order as one batch
+        (corro_process_fully_buffered_batch): the rows gathered out of the device row pool, one apply.
+        Returns the per-pair results: 0 not applied, 1 applied with no row impacted, 2 applied with
+        rows impacted, negative = the pair's own gap bookkeeping refused it. engine: the MergeEngine the
+        rows are merged into (None: a list that brings no row)."""
+        n = len(pairs)
+        if n == 0:
+            return []
+        a = np.frombuffer(b"".join(bytes(p[0]) for p in pairs), np.uint8)
+        v = np.array([p[1] for p in pairs], np.uint64)
+        res = np.zeros(n, np.int32)
+        L.check(L.lib().corro_process_fully_buffered_batch(engine._h if engine is not None else None, self._h,
+                                                           a.ctypes.data, v.ctypes.data, n, res.ctypes.data))
+        return [int(r) for r in res]
+
 
 class Agent:
     """One node's writer: the device merge engine + its Bookie (agent.rs:480-482 single writer)."""
@@ -410,6 +426,15 @@ class Agent:
         r = C.c_int()
         L.check(L.lib().corro_process_fully_buffered(self.engine._h, self.bookie._h, actor, version, C.byref(r)))
         return bool(r.value)
+
+    def process_ready(self, pairs=None):
+        """Every ready version applied in one batch (Bookie.process_ready): `pairs` in list order, or what
+        take_ready() lists. Returns [(actor, version, result)]: result 0 not applied, 1 applied with no
+        row impacted, 2 applied with rows impacted (the versions to match, updates.match_extracted),
+        negative = refused by its own gap bookkeeping."""
+        pairs = self.take_ready() if pairs is None else list(pairs)
+        res = self.bookie.process_ready(self.engine, pairs)
+        return [(bytes(a), int(v), r) for (a, v), r in zip(pairs, res)]
 
     def sync_book(self):
         """The bookie as one sync book (Bookie.sync_book): what generate_sync reads, one row per actor in

@@ -362,6 +362,19 @@ struct Batch {  // application-order SoA assembled on the host
     }
 };
 
+// a key's host rows appended to the staging columns (their long values' bytes to H.data)
+void host_rows_push(corro::ImgHostRows &H, const std::vector<HostRow> &rows) {
+    for (const HostRow &r : rows) {
+        H.pk.push_back(r.pk); H.v0.push_back(r.v0); H.v1.push_back(r.v1); H.ts.push_back(r.ts);
+        H.cv.push_back(r.cv); H.dbv.push_back(r.dbv); H.tcid.push_back(r.tcid); H.cl.push_back(r.cl);
+        H.seq.push_back(r.seq); H.site.push_back(r.site); H.vt.push_back(r.vt); H.vl.push_back(r.vl);
+        const bool lv = is_long(r.vt, r.vl) && !r.lv.empty();
+        H.voff.push_back(lv ? H.data.size() : 0);
+        H.vsz.push_back(lv ? (uint32_t)r.lv.size() : 0);
+        if (lv) H.data.insert(H.data.end(), r.lv.begin(), r.lv.end());
+    }
+}
+
 HostRow row_at(const corro_changes *in, uint64_t i, uint64_t ts) {
     HostRow r;
     r.pk = in->pk[i];
@@ -2410,6 +2423,158 @@ int process_multiple_changes(corro_ctx *ctx, corro_bookie *bk, const corro_chang
     return CORRO_OK;
 }
 
+// corro_process_fully_buffered_batch (corro_hip.h): process_fully_buffered_changes (util.rs:541-688) of
+// the n pairs in list order, as one batch. Everything up to the apply reads the bookie and writes
+// scratch; the commit runs only once the merge and the impact read-back have succeeded.
+int process_fully_buffered_batch(corro_ctx *ctx, corro_bookie *bk, const uint8_t *actor_ids, const uint64_t *versions,
+                                 uint64_t n, int32_t *result) {
+    const bool prof = std::getenv("CORRO_AGENT_PROFILE") != nullptr;  // stage marks, ms, on stderr
+    std::string prof_line;
+    auto t_prev = std::chrono::steady_clock::now();
+    auto stage = [&](const char *name) {
+        if (!prof) return;
+        const auto t = std::chrono::steady_clock::now();
+        char buf[64];
+        snprintf(buf, sizeof buf, " %s=%.3f", name, std::chrono::duration<double, std::milli>(t - t_prev).count());
+        prof_line += buf;
+        t_prev = t;
+    };
+    // 1. the walk: per actor in list order, on a copy of its Booked (taken at its first applicable pair)
+    struct ActorWalk {
+        corro::Booked *booked = nullptr;
+        corro::Booked next;
+        uint32_t site = 0;
+        bool known = false, copied = false;
+        std::vector<uint64_t> idx;       // its pairs, in list order
+        std::set<uint64_t> applied;      // its versions applied by an earlier pair of the list
+    };
+    std::map<ActorId, size_t> actor_at;
+    std::vector<ActorWalk> walks;
+    for (uint64_t i = 0; i < n; i++) {
+        const ActorId a = actor_of(actor_ids + 16 * i);
+        auto [it, fresh] = actor_at.emplace(a, walks.size());
+        if (fresh) {
+            walks.emplace_back();
+            ActorWalk &w = walks.back();
+            auto bit = bk->actors.find(a);
+            auto sit = bk->site_of.find(a);
+            if (bit != bk->actors.end() && sit != bk->site_of.end()) {  // (else "version not found in cache")
+                w.booked = &bit->second;
+                w.site = sit->second;
+                w.known = true;
+            }
+        }
+        walks[it->second].idx.push_back(i);
+    }
+    stage("group");
+    std::vector<int32_t> res(n, 0);
+    std::vector<uint32_t> site_of_pair(n, 0);
+    uint64_t napplied = 0;
+    for (ActorWalk &w : walks) {
+        if (!w.known) continue;
+        for (uint64_t i : w.idx) {
+            const uint64_t v = versions[i];
+            if (w.applied.count(v)) continue;  // applied by an earlier pair: its rows and seq book are gone
+            const corro::Booked &cur = w.copied ? w.next : *w.booked;
+            auto pit = cur.partials.find(v);
+            if (pit == cur.partials.end()) continue;
+            if (pit->second.seqs.has_gap(0, pit->second.last_seq)) continue;  // gaps: abort
+            if (!w.copied) {
+                w.next = *w.booked;
+                w.copied = true;
+            }
+            // insert_db([v..=v]) of this version alone (util.rs:648-654). It leaves its object modified
+            // when it fails, so it runs on the fields it reads (needed, max) and the partials it would
+            // drop -- those inside a deleted gap -- are dropped from the copy once it has succeeded.
+            // (A single version's insert_db deletes every gap its INSERTs could collide with, so no
+            // bookie the agent calls or corro_bookie_load build reaches the refusal below: it is there
+            // because insert_db can return it, and no test can drive it through the C ABI.)
+            corro::Booked t;
+            t.needed = w.next.needed;
+            t.has_max = w.next.has_max;
+            t.max = w.next.max;
+            RangeSet vs;
+            vs.insert(v, v);
+            std::vector<Range> removed;
+            if (!t.insert_db(vs, &removed, nullptr)) {  // UNIQUE constraint failed: __corro_bookkeeping_gaps.start
+                res[i] = CORRO_E_INVALID;
+                continue;
+            }
+            w.next.needed = std::move(t.needed);
+            w.next.has_max = t.has_max;
+            w.next.max = t.max;
+            for (const Range &r : removed)
+                w.next.partials.erase(w.next.partials.lower_bound(r.first), w.next.partials.upper_bound(r.second));
+            w.applied.insert(v);
+            res[i] = 1;
+            site_of_pair[i] = w.site;
+            napplied++;
+        }
+    }
+    stage("walk");
+    if (!napplied) {
+        std::copy(res.begin(), res.end(), result);
+        return CORRO_OK;
+    }
+    // 2. the piece list: the applied pairs in list order, a key's segments in seq0 order (ORDER BY
+    // db_version, seq); host-held keys' rows staged
+    std::vector<corro::ImgPiece> pool_pieces, host_pieces;
+    corro::ImgHostRows hrows;
+    std::vector<uint64_t> ver_off{0}, pair_of;
+    std::vector<std::pair<uint32_t, uint64_t>> sv;
+    uint64_t nrows = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        if (res[i] != 1) continue;
+        const uint32_t site = site_of_pair[i];
+        if (const BufEntry *e = bk->buffered.find({site, (int64_t)versions[i]})) {
+            if (e->segs.any_pending()) return fail(CORRO_E_INVALID, "the bookie holds a segment whose copy is pending");
+            if (!e->rows.empty()) {
+                host_pieces.push_back({hrows.size(), nrows, e->rows.size()});
+                nrows += e->rows.size();
+                host_rows_push(hrows, e->rows);
+            }
+            for (const PoolSeg &g : e->segs) {
+                if (!g.n) continue;
+                pool_pieces.push_back({g.off, nrows, g.n});
+                nrows += g.n;
+            }
+        }  // (else rows_present is false: applied with no row, util.rs:602-626)
+        ver_off.push_back(nrows);
+        pair_of.push_back(i);
+        sv.emplace_back(site, versions[i]);
+    }
+    if (nrows >= (1ULL << 31))
+        return fail(CORRO_E_RANGE, "the list's rows exceed one corro_apply_batch (2^31 - 1 changes): split the list");
+    if (nrows && !ctx) return fail(CORRO_E_INVALID, "NULL context for a list that brings rows");
+    stage("pieces");
+    // 3. one gather, one apply, the impacted answers
+    std::vector<uint32_t> any(napplied, 0);
+    corro::ReadyBatch rb;
+    if (nrows) TRY_RC(corro::ready_batch_gather(ctx, bk->pool, pool_pieces, hrows, host_pieces, ver_off, nrows, &rb));
+    stage("gather");
+    if (fault_armed("ready_gather")) return fail(CORRO_E_DEVICE, "injected fault (CORRO_FAULT): ready_gather");
+    if (nrows) {
+        corro_apply_out ao{};
+        ao.impact = rb.impact;
+        TRY_RC(corro_apply_batch(ctx, &rb.batch, CORRO_MEM_DEVICE, &ao));
+        stage("apply");
+        TRY_RC(corro::ready_batch_impacted(ctx, rb, any));
+        stage("impacted");
+    }
+    // 4. commit: everything below only records what the successful transactions did
+    clear_buffered_each(bk, sv);
+    compact_tables(bk);
+    stage("clear");
+    for (ActorWalk &w : walks)
+        if (w.copied) std::swap(*w.booked, w.next);
+    for (uint64_t k = 0; k < napplied; k++) res[pair_of[k]] = any[k] ? 2 : 1;
+    std::copy(res.begin(), res.end(), result);
+    stage("swap");
+    if (prof) fprintf(stderr, "[corro ready] pairs=%llu applied=%llu rows=%llu ms:%s\n", (unsigned long long)n,
+                      (unsigned long long)napplied, (unsigned long long)nrows, prof_line.c_str());
+    return CORRO_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2497,6 +2662,29 @@ int corro_process_fully_buffered(corro_ctx *ctx, corro_bookie *bk, const uint8_t
     for (uint8_t x : impact) total += x;
     if (impacted) *impacted = total > 0;
     return CORRO_OK;
+}
+
+// process_fully_buffered_changes of n (actor, version) pairs in list order, as one batch (the contract is
+// stated at the declaration, corro_hip.h). A failure after the merge wrote the state (the impact
+// read-back, a host exception in the commit) poisons the context, as for corro_process_multiple_changes.
+int corro_process_fully_buffered_batch(corro_ctx *ctx, corro_bookie *bk, const uint8_t *actor_ids,
+                                       const uint64_t *versions, uint64_t n, int32_t *result) {
+    if (!bk || (n && (!actor_ids || !versions || !result))) return fail(CORRO_E_INVALID, "NULL argument");
+    if (n == 0) return CORRO_OK;
+    const uint64_t mark0 = ctx ? corro::ctx_write_mark(ctx) : 0;
+    int rc;
+    try {
+        rc = process_fully_buffered_batch(ctx, bk, actor_ids, versions, n, result);
+    } catch (const std::bad_alloc &) {
+        rc = fail(CORRO_E_NOMEM, "host allocation failed in process_fully_buffered_batch");
+    } catch (const std::exception &e) {
+        rc = fail(CORRO_E_INVALID, std::string("process_fully_buffered_batch: ") + e.what());
+    } catch (...) {
+        rc = fail(CORRO_E_INVALID, "process_fully_buffered_batch: unknown host exception");
+    }
+    if (rc != CORRO_OK && ctx && corro::ctx_write_mark(ctx) != mark0)
+        corro::ctx_poison(ctx, " (after the merge: the context is poisoned until corro_state_reset)");
+    return rc;
 }
 
 // ---- per-actor Booked views -------------------------------------------------------------------
@@ -2947,15 +3135,7 @@ int image_books(const corro_bookie *bk, ImageBooks &B) {
         if (!x.val.rows.empty()) {
             B.host_pieces.push_back({H.size(), B.nrows, x.val.rows.size()});
             B.nrows += x.val.rows.size();
-            for (const HostRow &r : x.val.rows) {
-                H.pk.push_back(r.pk); H.v0.push_back(r.v0); H.v1.push_back(r.v1); H.ts.push_back(r.ts);
-                H.cv.push_back(r.cv); H.dbv.push_back(r.dbv); H.tcid.push_back(r.tcid); H.cl.push_back(r.cl);
-                H.seq.push_back(r.seq); H.site.push_back(r.site); H.vt.push_back(r.vt); H.vl.push_back(r.vl);
-                const bool lv = is_long(r.vt, r.vl) && !r.lv.empty();
-                H.voff.push_back(lv ? H.data.size() : 0);
-                H.vsz.push_back(lv ? (uint32_t)r.lv.size() : 0);
-                if (lv) H.data.insert(H.data.end(), r.lv.begin(), r.lv.end());
-            }
+            host_rows_push(H, x.val.rows);
         }
     }
     Fnv f;

@@ -209,6 +209,25 @@ struct ImgSeg {
 int bookimg_load_rows(corro_ctx *ctx, DevBufPool *pool, const corro_changes *rows, int mem, const uint8_t *site_ids,
                       uint32_t nsites, std::vector<ImgSeg> &segs, ImgHostRows &hrows);
 
+// ---- the ready drain (ready_batch.hip: the device half of corro_process_fully_buffered_batch) ----
+// The batch of a list of ready versions, gathered in list order into the context's scratch (valid until
+// the next drain on the context): pool_pieces name pool rows, host_pieces rows of `hrows`; together
+// their dst ranges tile [0, nrows), each list ascending by dst, no piece empty. ver_off (nver + 1
+// entries, ver_off[0] = 0, ver_off[nver] = nrows) is the batch row range of every version. hrows.data
+// becomes the batch's val_data. Writes scratch only. nrows = 0: nothing is done and no device is needed.
+struct ReadyBatch {
+    corro_changes batch{};             // device SoA, application order
+    uint8_t *impact = nullptr;         // nrows flags for corro_apply_batch to fill
+    const uint64_t *ver_off = nullptr; // device copy
+    uint32_t *any = nullptr;           // nver words
+    uint64_t nver = 0;
+};
+int ready_batch_gather(corro_ctx *ctx, const DevBufPool *pool, const std::vector<ImgPiece> &pool_pieces,
+                       const ImgHostRows &hrows, const std::vector<ImgPiece> &host_pieces,
+                       const std::vector<uint64_t> &ver_off, uint64_t nrows, ReadyBatch *out);
+// after the apply filled rb.impact: any[k] = 1 when a row of version k has its flag set (one small D2H)
+int ready_batch_impacted(corro_ctx *ctx, const ReadyBatch &rb, std::vector<uint32_t> &any);
+
 // Batched gap bookkeeping (corro_booked_insert_db_batch, gaps.hip) for a call with many actors:
 // host CSR in (per actor: booked max or -1, needed gaps, this call's versions), host arrays out
 // (per actor: new max, DELETE rows, INSERT rows, new gaps, status).

@@ -314,6 +314,9 @@ struct corro_ctx {
     // row reads (row_read.hip): [0] staged host keys, the per-key columns, row_off and rocPRIM temp, [1] the
     // per-row value offsets and staged host rows
     corro::DevBuf d_read[2];
+    // the ready drain (ready_batch.hip): the pieces, ver_off, the per-version words, staged host rows, the
+    // gathered batch and its impact flags
+    corro::DevBuf d_ready;
     corro::DevBuf d_match_base;   // u32 per table (+ 1): its first column slot
     bool match_base_ready = false;
     bool wire_schema_ready = false;

@@ -696,6 +696,44 @@ int corro_bookie_take_ready(corro_bookie *bk, uint8_t *actors, uint64_t *version
 /* process_fully_buffered_changes (util.rs:541-688) */
 int corro_process_fully_buffered(corro_ctx *ctx, corro_bookie *bk, const uint8_t *actor_id, uint64_t version,
                                  int *impacted);
+/* process_fully_buffered_changes (util.rs:541-688) of n (actor, version) pairs -- what
+ * corro_bookie_take_ready lists -- as ONE batch: equivalent, pair for pair, to calling
+ * corro_process_fully_buffered on the pairs in list order (the reference applies them one transaction
+ * each in notification order, apply_fully_buffered_changes_loop, util.rs:395-422; the merge is a left
+ * fold, so the transactions in order are one batch in application order). The rows are gathered out of
+ * the bookie's device row pool into the batch on the device (one gather, a key's segments in seq order:
+ * ORDER BY db_version, seq, :611-622), merged by one corro_apply_batch, and the per-pair
+ * rows_impacted > 0 answers (:632-664) read off its impact flags; no pool row visits the host. The rows
+ * of keys the bookie holds on the host (long values, non-canonical rows) are staged to the device once.
+ * The merged state, crsql_db_versions, the per-table committed counts (untouched, as by the one-by-one
+ * call) and the bookie afterwards equal the one-by-one calls'. actor_ids: 16 * n bytes; result: n
+ * entries, host memory:
+ *    0  not applied: the one-by-one call returns OK without touching anything -- an actor the bookie
+ *       does not hold, no partial at that version, seq gaps in 0 ..= last_seq (:569-584) -- or the pair
+ *       repeats a pair applied earlier in the list (the one-by-one call would commit an empty
+ *       transaction that changes nothing)
+ *    1  applied, rows_impacted == 0 (a complete seq book without a buffered row, :602-626, is applied
+ *       with no row)
+ *    2  applied, rows_impacted > 0
+ *   <0  a corro_status: the pair's own insert_db([v ..= v]) (:648-654) fails (UNIQUE constraint failed:
+ *       __corro_bookkeeping_gaps.start). The pair is left out of the batch, its bookie entries stay as
+ *       they were, the other pairs proceed and the call returns CORRO_OK.
+ * Each actor's pairs are walked in list order on a copy of its Booked, every version with its own
+ * insert_db; after the merge the applied keys' buffered rows and seq books are cleared and the copies
+ * swapped in. The call neither reads nor drains the ready list, and adds nothing to it: a pair the
+ * caller passes without having taken it with corro_bookie_take_ready is still listed there afterwards,
+ * as after the one-by-one call; passed again in a later call it finds its partial and no row, and is
+ * applied as a version without rows (result 1), which changes nothing.
+ * Failure atomicity: everything before the apply reads the bookie and writes scratch only, so a failure
+ * there (or in the apply before its first merge write) returns the error with the state and the bookie
+ * as they were, `result` unwritten; CORRO_FAULT=ready_gather injects one between the gather and the
+ * apply. A failure after the merge began writing poisons the context ("Failure atomicity" above); the
+ * bookie then keeps none of the call's versions. More rows than one corro_apply_batch takes
+ * (2^31 - 1): CORRO_E_RANGE before anything is written; the caller splits the list. n == 0 does nothing.
+ * A list that brings no row (no pair applicable, or only versions without rows) touches no device, and
+ * ctx may then be NULL. */
+int corro_process_fully_buffered_batch(corro_ctx *ctx, corro_bookie *bk, const uint8_t *actor_ids,
+                                       const uint64_t *versions, uint64_t n, int32_t *result);
 
 int corro_bookie_last(corro_bookie *bk, const uint8_t *actor_id, int64_t *max);
 int corro_bookie_needed(corro_bookie *bk, const uint8_t *actor_id, uint64_t *start, uint64_t *end, uint64_t cap,
