@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("CORRO_HIP_LIB") or os.path.join(HERE, "libcorro_hip.s
 CORRO_OK = 0
 ERRORS = {-1: "CORRO_E_INVALID", -2: "CORRO_E_NOMEM", -3: "CORRO_E_DEVICE",
           -4: "CORRO_E_UNKNOWN_TABLE", -5: "CORRO_E_UNKNOWN_COLUMN", -6: "CORRO_E_RANGE",
-          -7: "CORRO_E_NO_DEVICE"}
+          -7: "CORRO_E_NO_DEVICE", -8: "CORRO_E_CONSTRAINT"}
 CORRO_MEM_HOST, CORRO_MEM_DEVICE, CORRO_MEM_DEVICE_HEADERS = 0, 1, 2
 CORRO_PAYLOAD_SYNC, CORRO_PAYLOAD_UNI = 0, 1
 
@@ -49,6 +49,7 @@ EXPORTS = [
     "corro_bookie_save", "corro_bookie_load",
     "corro_pk_find", "corro_pk_find_device", "corro_read_rows",
     "corro_process_fully_buffered_batch",
+    "corro_local_write", "corro_local_bound", "corro_pk_count",
 ]
 
 CORRO_CS_FULL, CORRO_CS_EMPTY, CORRO_CS_EMPTY_SET = 0, 1, 2
@@ -57,6 +58,8 @@ CORRO_TCID_UNKNOWN = 0xFFFFFFFF
 CORRO_VAL_LONG = 255  # val_len of a TEXT/BLOB value longer than 16 bytes
 CORRO_PK_ABSENT = 0xFFFFFFFFFFFFFFFF  # corro_pk_find: a key the intern table does not hold
 CORRO_READ_VALUES = 1  # corro_read_in.flags: attach long values' bytes
+CORRO_OP_INSERT, CORRO_OP_UPDATE, CORRO_OP_UPSERT, CORRO_OP_DELETE = 0, 1, 2, 3  # corro_local_in.kind
+CORRO_E_CONSTRAINT = -8
 
 
 class CorroError(RuntimeError):
@@ -317,6 +320,20 @@ class ReadOut(C.Structure):
                 ("val_data", C.c_void_p)]
 
 
+class LocalIn(C.Structure):
+    _fields_ = [("nops", C.c_uint64), ("kind", C.c_void_p), ("table", C.c_void_p), ("pk", C.c_void_p),
+                ("cell_off", C.c_void_p), ("ncells", C.c_uint64), ("cid", C.c_void_p), ("val0", C.c_void_p),
+                ("val1", C.c_void_p), ("val_type", C.c_void_p), ("val_len", C.c_void_p), ("val_off", C.c_void_p),
+                ("val_size", C.c_void_p), ("val_data", C.c_void_p), ("val_data_len", C.c_uint64), ("ts", C.c_uint64),
+                ("site", C.c_uint32)]
+
+
+class LocalOut(C.Structure):
+    _fields_ = [("cap", C.c_uint64), ("val_data_cap", C.c_uint64), ("nrows", C.c_uint64), ("db_version", C.c_int64),
+                ("last_seq", C.c_uint64), ("val_data_len", C.c_uint64), ("rows", Rows), ("val_off", C.c_void_p),
+                ("val_size", C.c_void_p), ("val_data", C.c_void_p), ("op_result", C.c_void_p)]
+
+
 _lib = None
 
 
@@ -442,6 +459,9 @@ def lib():
         "corro_pk_find_device": (i32, [vp, u32, vp, vp, u64, vp]),
         "corro_read_rows": (i32, [vp, C.POINTER(ReadIn), i32, C.POINTER(ReadOut), i32]),
         "corro_pk_canonical": (i32, [C.c_char_p, u64, vp, u64, vp]),
+        "corro_local_write": (i32, [vp, vp, vp, C.POINTER(LocalIn), i32, C.POINTER(LocalOut)]),
+        "corro_local_bound": (i32, [vp, vp, vp, vp, u64, vp]),
+        "corro_pk_count": (i32, [vp, u32, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)

@@ -15,6 +15,7 @@ import numpy as np
 from . import _lib as L
 from .engine import MergeEngine
 from .sync import SyncStateV1
+from ._twopass import Mem
 
 
 @dataclass
@@ -214,9 +215,10 @@ class Agent:
         self.actor_id = actor_id
         self.site_ids = {}      # ordinal -> 16-byte site id (crsql_site_id)
 
-    def row_keys(self, changes):
+    def row_keys(self, changes, find_only=False):
         """Row keys of the changes' primary keys: an INTEGER pk is its own key; an interned table's
-        pk (pack_columns bytes, or an int packed as one INTEGER column) goes through corro_pk_keys."""
+        pk (pack_columns bytes, or an int packed as one INTEGER column) goes through corro_pk_keys, or with
+        find_only through corro_pk_find (CORRO_PK_ABSENT for a key the table does not hold; nothing interned)."""
         from .wire import pack_int_pk, unpack_int_pk
         keys = np.zeros(len(changes), np.uint64)
         by_table = {}
@@ -231,7 +233,7 @@ class Agent:
             else:
                 keys[j] = ch.pk & 0xFFFFFFFFFFFFFFFF
         for table, (idx, packed) in by_table.items():
-            keys[idx] = self.engine.pk_keys(table, packed)
+            keys[idx] = self.engine.pk_find(table, packed) if find_only else self.engine.pk_keys(table, packed)
         return keys
 
     def site(self, site_id):
@@ -407,6 +409,110 @@ class Agent:
         from . import updates
         res = self.match_changes(processed, dec, filters)
         return res, updates.read_candidates(self.engine, res, values=values)
+
+    def local_write(self, statements, ts=0, device=False):
+        """One local transaction (corro_local_write): statements = ("insert" | "update" | "upsert" | "delete",
+        table, pk, {column: value}) tuples in execution order, names and pks resolved like row_keys. The
+        changes are computed and merged on the device and the version is booked for self.actor_id. Returns
+        (db_version, last_seq, changes): the version's surviving Change list in seq order, (0, 0, []) when
+        the transaction wrote no clock. The raw result (what broadcast_frames takes) is kept in
+        self.last_local; device=True passes the statements as CUDA tensors and keeps that result on the GPU.
+        Interned tables: the pks of inserts and upserts are interned before the call (a new row needs its
+        key), so a transaction that then fails has still grown the intern table by those keys, as a rolled
+        back transaction leaves no trace in cr-sqlite's __crsql_pks but here leaves unused ids; the pks of
+        updates and deletes are only looked up (an unknown one names an absent row) and never intern."""
+        kinds = {"insert": L.CORRO_OP_INSERT, "update": L.CORRO_OP_UPDATE, "upsert": L.CORRO_OP_UPSERT,
+                 "delete": L.CORRO_OP_DELETE}
+        n = len(statements)
+        site = self.site(self.actor_id)
+        tix = {name: i for i, (name, _c) in enumerate(self.engine.schema)}
+        ops = {"kind": np.zeros(n, np.uint8), "table": np.zeros(n, np.uint32), "cell_off": np.zeros(n + 1, np.uint64)}
+        keyed = [Change(st[1], st[2], "-1", None, 0, 0, 0, self.actor_id, 0) for st in statements]
+        cid, v0, v1, vt, vl, voff, vsz, data, dlen = [], [], [], [], [], [], [], [], 0
+        for i, st in enumerate(statements):
+            kind, table, _pk = st[0], st[1], st[2]
+            cells = st[3] if len(st) > 3 and st[3] else {}
+            ops["kind"][i] = kinds[kind]
+            ops["table"][i] = tix[table]
+            for col, val in cells.items():
+                cid.append(self.engine.lookup(table, col) & 0xFFFF)
+                t, a, b, ln = encode_value(val)
+                v0.append(a), v1.append(b), vt.append(t), vl.append(ln)
+                raw = value_bytes(val) if ln == L.CORRO_VAL_LONG else b""
+                voff.append(dlen), vsz.append(len(raw))
+                data.append(raw)
+                dlen += len(raw)
+            ops["cell_off"][i + 1] = len(cid)
+        creates = [i for i, st in enumerate(statements) if st[0] in ("insert", "upsert")]
+        others = [i for i, st in enumerate(statements) if st[0] not in ("insert", "upsert")]
+        ops["pk"] = np.zeros(n, np.uint64)
+        ops["pk"][creates] = self.row_keys([keyed[i] for i in creates])
+        ops["pk"][others] = self.row_keys([keyed[i] for i in others], find_only=True)
+        ops.update(cid=np.array(cid, np.uint32), val0=np.array(v0, np.uint64), val1=np.array(v1, np.uint64),
+                   val_type=np.array(vt, np.uint8), val_len=np.array(vl, np.uint8))
+        if dlen:
+            ops.update(val_off=np.array(voff, np.uint64), val_size=np.array(vsz, np.uint32),
+                       val_data=np.frombuffer(b"".join(data), np.uint8))
+        self.last_local_ops = {k: ops[k] for k in ("kind", "table", "cell_off")}    # (host copies: local_bound's input)
+        if device:
+            import torch
+            sgn = {np.dtype(np.uint64): np.int64, np.dtype(np.uint32): np.int32}
+            ops = {k: torch.from_numpy(a.view(sgn.get(a.dtype, a.dtype)).copy()).cuda() for k, a in ops.items()}
+        res = self.engine.local_write(ops, ts, site, bookie=self.bookie, actor_id=self.actor_id)
+        self.last_local = dict(res, ts_call=int(ts), site_ord=site)
+        host = {k: (a.cpu().numpy() if device else a) for k, a in res.items() if hasattr(a, "shape")}
+        return res["version"], res["last_seq"], self._changes_of(host)
+
+    def _changes_of(self, rows):
+        """crsql_changes columns (host arrays, with val_off / val_size / val_data) -> Change list."""
+        out = []
+        raw = rows["val_data"].tobytes() if "val_data" in rows else b""
+        for k in range(len(rows["pk"])):
+            tc = int(rows["table_cid"][k])
+            table, cols = self.engine.schema[tc >> 16]
+            c = tc & 0xFFFF
+            ty, ln = int(rows["val_type"][k]), int(rows["val_len"][k])
+            m64 = 0xFFFFFFFFFFFFFFFF                 # (a device result's columns come back as signed tensors)
+            w0, w1 = int(rows["val0"][k]) & m64, int(rows["val1"][k]) & m64
+            if ty == L_NULL:
+                val = None
+            elif ty == 1:
+                val = w0 - (1 << 64) if w0 >> 63 else w0
+            elif ty == 2:
+                val = struct.unpack("<d", struct.pack("<Q", w0))[0]
+            else:
+                if ln == L.CORRO_VAL_LONG:
+                    o = int(rows["val_off"][k])
+                    b = raw[o:o + int(rows["val_size"][k])]
+                else:
+                    b = (w0.to_bytes(8, "big") + w1.to_bytes(8, "big"))[:ln]
+                val = b.decode() if ty == 3 else b
+            pk = int(rows["pk"][k]) & m64
+            if table in self.engine.interned:
+                pk = self.engine.pk_bytes(table, np.array([pk], np.uint64))[0]
+            out.append(Change(table, pk, "-1" if c == 0 else cols[c - 1], val, int(rows["col_version"][k]),
+                              int(rows["db_version"][k]), int(rows["seq"][k]), self.site_ids[int(rows["site"][k])],
+                              int(rows["cl"][k])))
+        return out
+
+    def broadcast_frames(self, result=None, max_buf_size=None, cluster_id=0):
+        """The broadcast of one local write (broadcast_changes, broadcast.rs:511-579): its rows as one span
+        0..=last_seq through corro_encode_changesets with CORRO_PAYLOAD_UNI, where they lie. result: a raw
+        engine.local_write result (None: the last local_write's). Returns encode_changesets' result ("buf"
+        holds the frames), or None for a transaction that wrote nothing."""
+        from . import serve
+        res = self.last_local if result is None else result
+        if not res["version"]:
+            return None
+        mem = Mem.of(res["pk"])
+        one = lambda v, dt: (mem._torch.tensor([v], dtype=mem._tdt[dt], device=mem.dev) if mem.on_dev
+                             else np.array([v], dt))
+        spans = {"site": one(res["site_ord"], np.uint32), "version": one(res["version"], np.int64),
+                 "last_seq": one(res["last_seq"], np.uint64), "ts": one(res["ts_call"], np.uint64),
+                 "seq_start": one(0, np.uint64), "seq_end": one(res["last_seq"], np.uint64),
+                 "row_off": one(0, np.uint64), "row_count": one(res["nrows"], np.uint64)}
+        return self.engine.encode_changesets(spans, res, max_buf_size or serve.MAX_CHANGES_BYTES_PER_MESSAGE,
+                                             L.CORRO_PAYLOAD_UNI, cluster_id)
 
     def take_ready(self):
         return self.bookie.take_ready()

@@ -44,6 +44,9 @@ int set_db_versions(corro_ctx *ctx, const std::vector<std::pair<uint32_t, uint64
 uint64_t ctx_write_mark(const corro_ctx *ctx);   // engine.hip: committed applies + set_db_version passes
 void ctx_poison(corro_ctx *ctx, const char *why);  // engine.hip
 bool ctx_poisoned(const corro_ctx *ctx);            // engine.hip
+// local_write.hip: the device half of corro_local_write
+int local_write_device(corro_ctx *ctx, const corro_local_in *in, int mem, corro_local_out *out,
+                       int (*pre_commit)(void *, uint64_t), void *arg);
 }  // namespace corro
 
 #define TRY_RC(x)                        \
@@ -2684,6 +2687,53 @@ int corro_process_fully_buffered_batch(corro_ctx *ctx, corro_bookie *bk, const u
     }
     if (rc != CORRO_OK && ctx && corro::ctx_write_mark(ctx) != mark0)
         corro::ctx_poison(ctx, " (after the merge: the context is poisoned until corro_state_reset)");
+    return rc;
+}
+
+// ---- local writes (corro_hip.h "local writes"; the device half is local_write.hip) -------------
+namespace {
+struct LocalBook {
+    corro_bookie *bk;
+    ActorId actor;
+    corro::Booked next;
+    bool booked = false;
+};
+// insert_db(db_version..=db_version) on a copy of the actor's Booked, committed only with the write
+int local_pre_commit(void *arg, uint64_t version) {
+    LocalBook &b = *static_cast<LocalBook *>(arg);
+    auto it = b.bk->actors.find(b.actor);
+    if (it != b.bk->actors.end()) b.next = it->second;
+    RangeSet v;
+    v.insert(version, version);
+    if (!b.next.insert_db(v, nullptr, nullptr))
+        return fail(CORRO_E_INVALID, "UNIQUE constraint failed: __corro_bookkeeping_gaps.start");
+    b.booked = true;
+    return CORRO_OK;
+}
+}  // namespace
+
+int corro_local_write(corro_ctx *ctx, corro_bookie *bk, const uint8_t *actor_id, const corro_local_in *in, int mem,
+                      corro_local_out *out) {
+    if (!ctx || !in || !out || (bk && !actor_id)) return fail(CORRO_E_INVALID, "NULL argument");
+    if (mem != CORRO_MEM_HOST && mem != CORRO_MEM_DEVICE) return fail(CORRO_E_INVALID, "bad mem kind");
+    if (in->nops && (!in->kind || !in->table || !in->pk || !in->cell_off)) return fail(CORRO_E_INVALID, "an op array is NULL");
+    if (in->ncells && (!in->cid || !in->val0)) return fail(CORRO_E_INVALID, "a cell array is NULL");
+    if (in->val_off && (!in->val_size || !in->val_type || !in->val_len || (in->val_data_len && !in->val_data)))
+        return fail(CORRO_E_INVALID, "long values need val_size, val_type, val_len and val_data");
+    if (corro::ctx_poisoned(ctx))
+        return fail(CORRO_E_DEVICE, "context poisoned: an earlier apply failed after it began writing the state; call "
+                                    "corro_state_reset");
+    int rc;
+    try {
+        LocalBook lb{bk, bk ? actor_of(actor_id) : ActorId{}, {}};
+        rc = corro::local_write_device(ctx, in, mem, out, bk ? local_pre_commit : nullptr, &lb);
+        if (rc == CORRO_OK && lb.booked) {
+            bk->actors[lb.actor] = std::move(lb.next);
+            bk->site_of[lb.actor] = in->site;
+        }
+    } catch (const std::bad_alloc &) {
+        rc = fail(CORRO_E_NOMEM, "host allocation failed in corro_local_write");
+    }
     return rc;
 }
 

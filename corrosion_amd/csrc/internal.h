@@ -180,6 +180,11 @@ __device__ inline uint32_t site_hash_find(const SiteHash &t, uint64_t lo, uint64
     }
 }
 
+// The device half of corro_local_write (local_write.hip): pre_commit(arg, db_version) runs once every check
+// has passed and before the first write; a non-zero return ends the call with that code.
+int local_write_device(corro_ctx *ctx, const corro_local_in *in, int mem, corro_local_out *out,
+                       int (*pre_commit)(void *, uint64_t), void *arg);
+
 // the rocPRIM kernels' first-use cost paid once per process and device (prims.hip)
 int prims_warm(corro_ctx *ctx);
 // the agent's pinned host areas for a call of `ncs` changesets (agent_dev.hip), ahead of the first call
@@ -317,6 +322,10 @@ struct corro_ctx {
     // the ready drain (ready_batch.hip): the pieces, ver_off, the per-version words, staged host rows, the
     // gathered batch and its impact flags
     corro::DevBuf d_ready;
+    // local writes (local_write.hip): [0] staged host statements, the per-op and per-cell columns and rocPRIM
+    // temp, [1] the write slots and their scans, [2] the per-row value offsets and staged host rows, [3] the
+    // surviving long values' bytes
+    corro::DevBuf d_local[4];
     corro::DevBuf d_match_base;   // u32 per table (+ 1): its first column slot
     bool match_base_ready = false;
     bool wire_schema_ready = false;

@@ -1259,6 +1259,13 @@ int corro_pk_keys_device(corro_ctx *ctx, uint32_t table, const uint8_t *bytes, c
     return pk_keys_device(ctx, table, r, n, keys, nullptr, nullptr);
 }
 
+int corro_pk_count(corro_ctx *ctx, uint32_t table, uint64_t *count) {
+    if (!ctx || !count) return fail(CORRO_E_INVALID, "NULL argument");
+    if (table >= ctx->tables.size()) return fail(CORRO_E_UNKNOWN_TABLE, "no such table index");
+    *count = table < ctx->pk.size() && ctx->pk[table].interned ? ctx->pk[table].n : 0;
+    return CORRO_OK;
+}
+
 int corro_pk_bytes(corro_ctx *ctx, uint32_t table, const uint64_t *keys, uint64_t n, uint8_t *bytes, uint64_t cap,
                    uint64_t *out_off) {
     if (!ctx || (n && (!keys || !out_off)) || (cap && !bytes)) return fail(CORRO_E_INVALID, "NULL argument");

@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
-from ._twopass import Mem, _int_dtype_ok, _is_torch, two_pass
+from ._twopass import Mem, TwoPass, _int_dtype_ok, _is_torch, two_pass
 
 BATCH_FIELDS = {"pk": np.uint64, "table_cid": np.uint32, "col_version": np.int64,
                 "db_version": np.int64, "cl": np.uint32, "seq": np.uint32, "site": np.uint32,
@@ -219,6 +219,12 @@ class MergeEngine:
         L.check(L.lib().corro_pk_find(self._h, t, buf.ctypes.data, off.ctypes.data, len(packed), keys.ctypes.data))
         return keys[:len(packed)]
 
+    def pk_count(self, table):
+        """Keys the table's intern table holds (corro_pk_count); 0 for a table keyed by its INTEGER pk."""
+        c = C.c_uint64()
+        L.check(L.lib().corro_pk_count(self._h, self.table_index(table), C.byref(c)))
+        return c.value
+
     def pk_bytes(self, table, keys):
         """Canonical packed pk bytes of row keys of one table."""
         t = self.table_index(table)
@@ -357,6 +363,59 @@ class MergeEngine:
                 res["long_values"] = {int(i): raw[int(off[i]):int(off[i]) + int(size[i])] for i in np.nonzero(size)[0]}
             else:
                 res["long_values"] = self.long_values(res)
+        return res
+
+    def local_bound(self, kind, table, cell_off):
+        """An upper bound of the rows one local_write of these ops returns (corro_local_bound; host arrays)."""
+        kind = np.ascontiguousarray(kind, np.uint8)
+        table = np.ascontiguousarray(table, np.uint32)
+        cell_off = np.ascontiguousarray(cell_off, np.uint64)
+        b = C.c_uint64()
+        L.check(L.lib().corro_local_bound(self._h, kind.ctypes.data, table.ctypes.data, cell_off.ctypes.data, len(kind),
+                                          C.byref(b)))
+        return b.value
+
+    def local_write(self, ops, ts, site, bookie=None, actor_id=None, cap=None, val_data_cap=None):
+        """One local transaction (corro_local_write): ops = {"kind" u8, "table" u32, "pk" u64, "cell_off" u64
+        (nops + 1), "cid" u32, "val0", "val1" u64, "val_type", "val_len" u8 per cell, and for long values
+        "val_off", "val_size", "val_data"} as numpy arrays (host) or CUDA tensors (device: only the totals
+        reach the host). cap: the capacity of the returned rows (None: ncols + 1 per op over the widest
+        table, plus the cells, which bounds any transaction). Returns "version" (the db_version; 0: nothing written),
+        "last_seq", "nrows", the crsql_changes columns of the version's surviving changes in ascending seq
+        (what encode_changesets takes), "val_off" / "val_size" / "val_data" / "val_data_len" and
+        "op_result" per op. bookie / actor_id: the Bookie that books the version."""
+        mem = Mem.of(ops["pk"])
+        nops, ncells = mem.count(ops["pk"]), mem.count(ops["cid"])
+        s = L.LocalIn()
+        s.nops, s.ncells, s.ts, s.site = nops, ncells, int(ts), int(site)
+        fields = [("kind", np.uint8, nops), ("table", np.uint32, nops), ("pk", np.uint64, nops),
+                  ("cell_off", np.uint64, nops + 1), ("cid", np.uint32, ncells), ("val0", np.uint64, ncells)]
+        fields += [(k, dt, ncells) for k, dt in (("val1", np.uint64), ("val_type", np.uint8), ("val_len", np.uint8)) if k in ops]
+        dlen = mem.count(ops["val_data"]) if "val_data" in ops else 0
+        if dlen:
+            fields += [("val_off", np.uint64, ncells), ("val_size", np.uint32, ncells), ("val_data", np.uint8, None)]
+            s.val_data_len = dlen
+        keep = mem.fill(s, ops, fields)
+        if cap is None:
+            cap = nops * (max([len(c) for _n, c in self.schema] + [0]) + 1) + ncells
+        if val_data_cap is None:
+            val_data_cap = dlen + 24 * ncells
+        o = L.LocalOut()
+        o.cap, o.val_data_cap = cap, val_data_cap
+        tp = TwoPass(None, (), mem, o)
+        tp.bind(tuple(("rows." + k, dt, cap) for k, dt in ROW_FIELDS.items()) +
+                (("val_off", np.uint64, cap), ("val_size", np.uint32, cap), ("val_data", np.uint8, val_data_cap),
+                 ("op_result", np.uint8, nops)))
+        mem.sync()
+        L.check(L.lib().corro_local_write(self._h, bookie._h if bookie is not None else None, actor_id, C.byref(s),
+                                          mem.const, C.byref(o)))
+        del keep
+        n, vb = int(o.nrows), int(o.val_data_len)
+        res = {}
+        for k, a in tp.result().items():
+            k = k[5:] if k.startswith("rows.") else k
+            res[k] = a if k == "op_result" else a[:vb] if k == "val_data" else a[:n]
+        res.update(version=int(o.db_version), last_seq=int(o.last_seq), nrows=n, val_data_len=vb)
         return res
 
     def track_touched(self, on=True):

@@ -41,7 +41,8 @@ typedef enum {
     CORRO_E_UNKNOWN_TABLE = -4,  /* "no such table" (the INSERT would fail: util.rs:839-860) */
     CORRO_E_UNKNOWN_COLUMN = -5, /* unknown cid: cr-sqlite raises "SQL logic error" */
     CORRO_E_RANGE = -6,          /* value outside the engine's fixed-width encoding */
-    CORRO_E_NO_DEVICE = -7       /* no HIP device visible */
+    CORRO_E_NO_DEVICE = -7,      /* no HIP device visible */
+    CORRO_E_CONSTRAINT = -8      /* corro_local_write: INSERT of a live row ("UNIQUE constraint failed") */
 } corro_status;
 
 /* SQLite storage classes, numbered like corro-api-types ColumnType (lib.rs:300-307) */
@@ -191,6 +192,8 @@ int corro_pk_find(corro_ctx *ctx, uint32_t table, const uint8_t *bytes, const ui
                   uint64_t *keys);
 int corro_pk_find_device(corro_ctx *ctx, uint32_t table, const uint8_t *bytes, const uint64_t *off, uint64_t n,
                          uint64_t *keys);
+/* Keys the table's intern table holds (its next id); 0 for a table keyed by its INTEGER pk. Host only. */
+int corro_pk_count(corro_ctx *ctx, uint32_t table, uint64_t *count);
 /* Row keys of `table` -> canonical packed pk bytes (export, extraction): key i's bytes at
  * [out_off[i], out_off[i+1]); out_off holds n + 1 entries; CORRO_E_RANGE if cap < out_off[n]. */
 int corro_pk_bytes(corro_ctx *ctx, uint32_t table, const uint64_t *keys, uint64_t n, uint8_t *bytes, uint64_t cap,
@@ -1580,6 +1583,102 @@ typedef struct {
 } corro_read_out;
 
 int corro_read_rows(corro_ctx *ctx, const corro_read_in *in, int mem, corro_read_out *out, int pass);
+
+/* ------------------------------------------------------------------ local writes */
+
+/* One local transaction -> its changes, applied and returned for broadcast: what make_broadcastable_changes
+ * (corro-agent/src/api/public/mod.rs:53-138) and insert_local_changes (corro-types/src/change.rs:189-260) do
+ * on every API write, with cr-sqlite 0.17.0's CRR triggers computed on the device. The call is a list of row
+ * statements in execution order; it writes the merged state like a corro_apply_batch of the returned rows, and
+ * those rows are the arrays corro_encode_changesets takes (one span 0..=last_seq, CORRO_PAYLOAD_UNI: what
+ * broadcast_changes, broadcast.rs:511-579, sends).
+ *
+ * Semantics (pinned by tests/golden/local_write_kats.json, generated from the extension). Let L be the row's
+ * causal length as corro_read_rows defines it (0 if absent); the row is live iff L is odd.
+ *   db_version  the local site's next: its crsql_db_versions entry (0 if none) + 1, whatever other sites'
+ *               entries hold. A transaction that writes no clock (every UPDATE set an equal value, every
+ *               DELETE met a row that is not live) takes no db_version and returns no rows.
+ *   seq         every clock write takes the next seq from 0, in statement order and, inside a statement, the
+ *               sentinel first and then the columns by ascending cid. A later write of the same cell
+ *               replaces the earlier one, so the returned rows' seqs have holes; last_seq is the largest
+ *               seq written.
+ *   INSERT      of a row that is not live: every non-pk column in schema order (unlisted ones NULL) with
+ *               col_version 1 and cl = the new causal length. L == 0: cl 1 and no sentinel, except for a
+ *               table without non-pk columns (sentinel col_version 1, cl 1). L even: first a sentinel with
+ *               col_version = cl = L + 1. Of a live row: CORRO_E_CONSTRAINT.
+ *   UPDATE      of a live row: each listed value is converted by its column's affinity and written iff it
+ *               differs from the stored one by storage class and bytes (INTEGER 1 over REAL 1.0 differs;
+ *               a cell without a clock record reads as NULL; long values compare by length and bytes), with
+ *               col_version = the cell's (0 without a record) + 1 and cl = L, in ascending cid whatever the
+ *               order of the list. Of a row that is not live: nothing.
+ *   DELETE      of a live row: one sentinel, col_version = cl = L + 1, value NULL; the row's column clocks
+ *               are gone (a later INSERT restarts them at 1). Of a row that is not live: nothing.
+ *   UPSERT      INSERT ... ON CONFLICT(pk) DO UPDATE SET listed = excluded: INSERT when the row is not live,
+ *               else UPDATE of the listed columns.
+ *   site, ts    every returned row carries in->site, the call's db_version and in->ts.
+ * Out of scope: UPDATE of a primary key (cr-sqlite moves the clocks; it is not delete plus insert), INSERT OR
+ * REPLACE, column DEFAULTs, savepoints inside the transaction, schema changes.
+ *
+ * Single pass (the call mutates). out->cap is checked against the exact number of surviving rows before
+ * anything is written (CORRO_E_RANGE); corro_local_bound gives an upper bound. `mem` covers every array of
+ * both structs; with CORRO_MEM_DEVICE only the totals and the error words cross PCIe. rows' arrays are all
+ * required when a row is returned; val_off / val_size / val_data are optional (a long value's val1 is its
+ * arena handle either way, as in exports; with them its bytes are at val_data[val_off[k], + val_size[k]),
+ * val_data_cap >= val_data_len or CORRO_E_RANGE; in->val_data_len + 24 * in->ncells always suffices).
+ * Device arrays of 64-bit fields must be 16-byte aligned, as for corro_apply_batch.
+ *
+ * Errors, each before any write to the store, the arena, the intern table, crsql_db_versions or the bookie:
+ * CORRO_E_INVALID (a NULL required array, a bad kind or mem, an unregistered site, a table or cid outside the
+ * schema, cid 0, a cid twice in one op, cells on a DELETE, a malformed value), CORRO_E_CONSTRAINT (the error
+ * string names the lowest failing op index), CORRO_E_RANGE (cap, val_data_cap, 2^31 ops or cells, 2^32 clock
+ * writes), CORRO_E_DEVICE (a poisoned context). A failure inside the apply is corro_apply_batch's; a failure
+ * after the apply has committed (the handle pass, a download) poisons the context, since the store then holds
+ * a version the caller has neither rows nor a booking for. CORRO_AGENT_PROFILE in the environment prints the
+ * call's stage times on stderr (the stream is drained at every mark).
+ *
+ * Bookie: after a write with db_version > 0, db_version..=db_version is booked for actor_id in bk (insert_db,
+ * change.rs:242-250); a version the bookie already holds fails the call with CORRO_E_INVALID before any
+ * write. A NULL bk skips the booking. */
+enum { CORRO_OP_INSERT = 0, CORRO_OP_UPDATE = 1, CORRO_OP_UPSERT = 2, CORRO_OP_DELETE = 3 };
+
+typedef struct {
+    uint64_t nops;
+    const uint8_t *kind;                   /* nops: CORRO_OP_* */
+    const uint32_t *table;                 /* nops: table index */
+    const uint64_t *pk;                    /* nops: row key as in corro_changes.pk (interned: corro_pk_keys first) */
+    const uint64_t *cell_off;              /* nops + 1: op i lists cells [cell_off[i], cell_off[i + 1]) */
+    uint64_t ncells;
+    const uint32_t *cid;                   /* ncells: 1-based column */
+    const uint64_t *val0, *val1;           /* ncells: the value arrays of corro_changes, with their meanings */
+    const uint8_t *val_type, *val_len;     /* (val1, val_type, val_len optional as there) */
+    const uint64_t *val_off;
+    const uint32_t *val_size;
+    const uint8_t *val_data;
+    uint64_t val_data_len;
+    uint64_t ts;
+    uint32_t site;                         /* the local site's ordinal */
+} corro_local_in;
+
+typedef struct {
+    uint64_t cap;                          /* in: capacity of rows / val_off / val_size */
+    uint64_t val_data_cap;                 /* in: capacity of val_data */
+    uint64_t nrows;                        /* out */
+    int64_t db_version;                    /* out: 0 when nothing was written */
+    uint64_t last_seq;                     /* out */
+    uint64_t val_data_len;                 /* out */
+    corro_rows rows;                       /* the version's surviving changes in ascending seq */
+    uint64_t *val_off;
+    uint32_t *val_size;
+    uint8_t *val_data;
+    uint8_t *op_result;                    /* nops (optional): 0 = no effect, 1 = row written */
+} corro_local_out;
+
+int corro_local_write(corro_ctx *ctx, corro_bookie *bk, const uint8_t *actor_id, const corro_local_in *in, int mem,
+                      corro_local_out *out);
+/* Host only: an upper bound of nrows from host copies of kind, table and cell_off -- inserts and upserts count
+ * the table's columns + 1, updates their cells, deletes 1. */
+int corro_local_bound(corro_ctx *ctx, const uint8_t *kind, const uint32_t *table, const uint64_t *cell_off, uint64_t nops,
+                      uint64_t *bound);
 
 #ifdef __cplusplus
 }
