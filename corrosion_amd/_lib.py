@@ -50,6 +50,7 @@ EXPORTS = [
     "corro_pk_find", "corro_pk_find_device", "corro_read_rows",
     "corro_process_fully_buffered_batch",
     "corro_local_write", "corro_local_bound", "corro_pk_count",
+    "corro_query_rows",
 ]
 
 CORRO_CS_FULL, CORRO_CS_EMPTY, CORRO_CS_EMPTY_SET = 0, 1, 2
@@ -60,6 +61,10 @@ CORRO_PK_ABSENT = 0xFFFFFFFFFFFFFFFF  # corro_pk_find: a key the intern table do
 CORRO_READ_VALUES = 1  # corro_read_in.flags: attach long values' bytes
 CORRO_OP_INSERT, CORRO_OP_UPDATE, CORRO_OP_UPSERT, CORRO_OP_DELETE = 0, 1, 2, 3  # corro_local_in.kind
 CORRO_E_CONSTRAINT = -8
+CORRO_QUERY_KEYED, CORRO_QUERY_VALUES = 1, 2  # corro_query_in.flags
+# corro_query_in.term_op (CORRO_QOP_*), by the SQL spelling MergeEngine.query_rows takes
+QUERY_OPS = {"=": 0, "==": 0, "!=": 1, "<>": 1, "<": 2, "<=": 3, ">": 4, ">=": 5, "is null": 6, "is not null": 7}
+CORRO_QUERY_MAX_TERMS, CORRO_QUERY_MAX_GROUPS, CORRO_QUERY_MAX_PROJ = 64, 64, 256
 
 
 class CorroError(RuntimeError):
@@ -334,6 +339,18 @@ class LocalOut(C.Structure):
                 ("val_size", C.c_void_p), ("val_data", C.c_void_p), ("op_result", C.c_void_p)]
 
 
+class QueryIn(C.Structure):
+    _fields_ = [("table", C.c_uint32), ("flags", C.c_uint32), ("nkeys", C.c_uint64), ("keys", C.c_void_p),
+                ("ngroups", C.c_uint32), ("nterms", C.c_uint32)] + [(k, C.c_void_p) for k in (
+        "group_off", "term_col", "term_op", "val_type", "val_len", "val0", "val1", "const_off", "const_size",
+        "const_data")] + [("const_data_len", C.c_uint64), ("nproj", C.c_uint32), ("proj", C.c_void_p)]
+
+
+class QueryOut(C.Structure):
+    _fields_ = [("nrows", C.c_uint64), ("val_data_len", C.c_uint64)] + [(k, C.c_void_p) for k in (
+        "key_status", "key_index", "pk", "cl", "val_type", "val_len", "val0", "val1", "val_off", "val_size", "val_data")]
+
+
 _lib = None
 
 
@@ -462,6 +479,7 @@ def lib():
         "corro_local_write": (i32, [vp, vp, vp, C.POINTER(LocalIn), i32, C.POINTER(LocalOut)]),
         "corro_local_bound": (i32, [vp, vp, vp, vp, u64, vp]),
         "corro_pk_count": (i32, [vp, u32, vp]),
+        "corro_query_rows": (i32, [vp, C.POINTER(QueryIn), i32, C.POINTER(QueryOut), i32]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)

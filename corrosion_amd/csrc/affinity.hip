@@ -47,6 +47,7 @@
 
 #include "internal.h"
 #include "merge_kernels.h"
+#include "query_terms.h"
 
 namespace corro {
 
@@ -460,8 +461,10 @@ __device__ uint32_t aff_real_text(double r, uint8_t *out) {
 // The value a column of affinity `aff` stores for (ty, v0, text t). True = converted: *oty, *ov0
 // (INTEGER / REAL bits) or txt/len (TEXT, at most 24 bytes).
 // *sens: the conversion is not known to be version-independent (the header's PORTABLE rules).
+// comparing: the value is a comparison's operand, not a write to the column -- a REAL column leaves an
+// INTEGER result an INTEGER (SQLite compares it with the stored REAL exactly).
 __device__ bool aff_convert(uint32_t aff, uint32_t ty, uint64_t v0, const TextView &t, uint32_t *oty,
-                            uint64_t *ov0, uint8_t *txt, uint32_t *len, bool *sens) {
+                            uint64_t *ov0, uint8_t *txt, uint32_t *len, bool *sens, bool comparing = false) {
     *len = 0;
     *sens = false;
     if (aff == CORRO_AFF_BLOB || ty == CORRO_NULL || ty == CORRO_BLOB) return false;
@@ -513,7 +516,7 @@ __device__ bool aff_convert(uint32_t aff, uint32_t ty, uint64_t v0, const TextVi
             iv = i;
         }
     }
-    if (aff == CORRO_AFF_REAL && rt == CORRO_INTEGER) {
+    if (aff == CORRO_AFF_REAL && rt == CORRO_INTEGER && !comparing) {
         rt = CORRO_REAL;
         rv = (double)iv;
     }
@@ -647,6 +650,101 @@ int affinity_convert(corro_ctx *ctx, BatchDev &bd) {
     bd.cv1 = cv1;
     bd.cmeta = cmeta;
     bd.arena = ctx->d_arena.as<uint8_t>();
+    return CORRO_OK;
+}
+
+// The terms of a row query (query_terms.h) brought to their comparison form, one lane per term: the screen
+// of the caller's arrays, then aff_convert as a comparison applies it. Lanes also screen group_off and the
+// projection. Nothing outside the scratch `a` names is written.
+__global__ void __launch_bounds__(256) k_aff_query_consts(QConstArgs a) {
+    const uint32_t t = threadIdx.x;
+    bool bad = false, refused = false;
+    if (t <= a.ngroups && a.ngroups) {
+        const uint32_t g = a.group_off[t];
+        bad |= g > a.nterms || (t > 0 && a.group_off[t - 1] > g);
+        a.goff[t] = (uint8_t)min(g, a.nterms);
+    }
+    if (t < a.nproj) {
+        const uint32_t c = a.proj[t];
+        bad |= c > a.ncols;
+        a.projc[t] = (uint8_t)min(c, a.ncols);
+    }
+    if (t < a.nterms) {
+        const uint32_t col = a.term_col[t], op = a.term_op[t], ty = a.val_type[t], ln = a.val_len[t];
+        const uint64_t v0 = a.val0[t], v1 = a.val1[t];
+        const bool bytes = ty == CORRO_TEXT || ty == CORRO_BLOB, lng = ln == VLEN_LONG;
+        bool ok = op <= 7 && ty >= 1 && ty <= 5 && col <= a.ncols && !(col == 0 && a.interned);
+        ok = ok && (lng ? bytes : ln <= 16);
+        uint64_t off = 0, size = bytes ? ln : 0;
+        if (ok && lng) {
+            ok = a.const_off && a.const_size && a.const_data;
+            if (ok) {
+                off = a.const_off[t];
+                size = a.const_size[t];
+                ok = size > 16 && size < (1u << 24) && off <= a.const_data_len && size <= a.const_data_len - off;
+            }
+        }
+        if (ok && ty == CORRO_REAL) {
+            const double r = __longlong_as_double((long long)v0);
+            ok = r == r;  // NaN
+        }
+        QTerm q{};
+        if (ok) {
+            q.col = (uint8_t)col;
+            q.op = (uint8_t)op;
+            q.ty = (uint8_t)ty;
+            q.len = (uint32_t)size;
+            q.w0 = v0;
+            q.w1 = bytes ? v1 : 0;
+            if (lng) {
+                q.p = a.const_data + off;
+                q.w0 = q.w1 = 0;  // (a long constant's words are its first 16 bytes, whatever the caller gave)
+                for (uint32_t k = 0; k < 8; k++) {
+                    q.w0 |= (uint64_t)q.p[k] << (56 - 8 * k);
+                    q.w1 |= (uint64_t)q.p[8 + k] << (56 - 8 * k);
+                }
+            } else if (bytes) {  // the padding of an inline value compares as zero bytes never read
+                if (ln < 8) q.w0 &= ln ? ~0ULL << (64 - 8 * ln) : 0ULL;
+                if (ln < 16) q.w1 &= ln > 8 ? ~0ULL << (128 - 8 * ln) : 0ULL;
+            }
+            // column 0 exists on a table keyed by its INTEGER pk only: INTEGER affinity
+            const uint32_t aff = col == 0 ? (uint32_t)CORRO_AFF_INTEGER
+                                          : a.aff ? a.aff[a.table * (MAX_COLS + 1) + col] : (uint32_t)CORRO_AFF_BLOB;
+            const TextView tv{q.w0, q.w1, lng ? q.p : nullptr, size};
+            uint32_t oty = 0, olen = 0;
+            uint64_t ov0 = 0;
+            uint8_t txt[32];
+            bool sens = false;
+            if (op < 6 && aff_convert(aff, ty, v0, tv, &oty, &ov0, txt, &olen, &sens, true)) {
+                refused = sens && a.portable;
+                q.ty = (uint8_t)oty;
+                q.p = nullptr;
+                q.w0 = ov0;
+                q.w1 = 0;
+                q.len = 0;
+                if (oty == CORRO_TEXT) {
+                    uint8_t *slot = a.txt + (size_t)t * QTXT_SLOT;
+                    q.w0 = 0;
+                    q.len = olen;
+                    for (uint32_t k = 0; k < olen && k < QTXT_SLOT; k++) {
+                        slot[k] = txt[k];
+                        if (k < 8) q.w0 |= (uint64_t)txt[k] << (56 - 8 * k);
+                        else if (k < 16) q.w1 |= (uint64_t)txt[k] << (56 - 8 * (k - 8));
+                    }
+                    if (olen > 16) q.p = slot;
+                }
+            }
+        }
+        a.terms[t] = q;
+        bad |= !ok;
+    }
+    if (bad) atomicOr(&a.err[0], 1u);
+    if (refused) atomicOr(&a.err[1], 1u);
+}
+
+int query_consts(corro_ctx *ctx, const QConstArgs &a) {
+    hipLaunchKernelGGL(k_aff_query_consts, dim3(1), dim3(256), 0, ctx->stream, a);
+    CORRO_HIP_TRY(hipGetLastError());
     return CORRO_OK;
 }
 

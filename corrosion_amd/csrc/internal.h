@@ -326,6 +326,11 @@ struct corro_ctx {
     // temp, [1] the write slots and their scans, [2] the per-row value offsets and staged host rows, [3] the
     // surviving long values' bytes
     corro::DevBuf d_local[4];
+    // row queries (query.hip): [0] staged host inputs, the prepared terms, the error and count words, the
+    // table form's candidates or the keyed form's per-key columns, the selected entries and rocPRIM temp,
+    // [1] the table form's sorted candidates and the sort's temp, [2] the per-cell value offsets and staged
+    // host outputs
+    corro::DevBuf d_query[3];
     corro::DevBuf d_match_base;   // u32 per table (+ 1): its first column slot
     bool match_base_ready = false;
     bool wire_schema_ready = false;
@@ -374,3 +379,14 @@ struct corro_ctx {
     hipEvent_t ev[8] = {};
     float last_ms[9] = {};        // apply stages [0..5], k_needs / extract count [6], fill [7], extract index build [8]
 };
+
+namespace corro {
+// Is table t keyed by interned ids (pkeys.hip), and how many keys its intern table holds. corro_ctx::pk is
+// sized lazily by the pk calls, so a context that has made none holds fewer entries than tables: the index
+// is checked against the vector's own size, and nothing is resized -- a reader leaves the context as it was.
+inline bool pk_interned(const corro_ctx *ctx, uint32_t t, uint64_t *count = nullptr) {
+    const bool on = t < ctx->pk.size() && ctx->pk[t].interned;
+    if (count) *count = on ? ctx->pk[t].n : 0;
+    return on;
+}
+}  // namespace corro

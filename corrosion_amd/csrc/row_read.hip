@@ -16,9 +16,10 @@
 //                write consecutive elements of every column, and a 127-column row is spread over 128
 //                lanes instead of walked by one.
 //   scan of val_size -> val_off.
-//   k_rd_values  (pass 1) per 16 OUTPUT bytes of val_data: the value that holds the first byte by
-//                binary search in val_off, the bytes gathered from the arena, one 16-B store when the
-//                destination is aligned (byte stores else, and for the last partial chunk).
+//   k_gather_values (pass 1; value_gather.h, shared with query.hip) per 16 OUTPUT bytes of val_data: the
+//                value that holds the first byte by binary search in val_off, the bytes gathered from the
+//                arena, one 16-B store when the destination is aligned (byte stores else, and for the
+//                last partial chunk).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -27,6 +28,7 @@
 #include "merge_kernels.h"
 #include "scratch.h"
 #include "search.h"
+#include "value_gather.h"
 
 namespace corro {
 int prim_inclusive_scan_u32_u64(void *temp, size_t *temp_bytes, const uint32_t *in, uint64_t *out, uint64_t n,
@@ -132,34 +134,6 @@ __global__ void k_rd_fill(RdDev d) {
         const bool lv = is_long(r.meta);
         d.val_size[k] = lv ? (uint32_t)(r.v1 & 0xFFFFFFu) : 0u;
         d.vsrc[k] = lv ? r.v1 >> 24 : 0ULL;
-    }
-}
-
-__global__ void k_rd_values(RdDev d) {
-    const uint64_t base = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * 16;
-    if (base >= d.vbytes) return;
-    // voff[0] = 0 <= base < voff[nrows] = vbytes: record k holds byte `base` (its size is not 0)
-    uint64_t k = ub64(d.voff, d.nrows + 1, base) - 1;
-    if (k >= d.nrows) return;                          // (never)
-    const uint32_t nb = (uint32_t)min((uint64_t)16, d.vbytes - base);
-    uint32_t w[4] = {};                                // (statically indexed: the loop is unrolled)
-#pragma unroll
-    for (uint32_t b = 0; b < 16; b++) {
-        if (b >= nb) break;
-        const uint64_t pos = base + b;
-        // (a value is longer than 16 bytes: a chunk leaves its first value at most once; the records
-        // between two long values hold no byte and are searched over, not walked)
-        if (pos >= d.voff[k + 1]) k = min(ub64(d.voff, d.nrows + 1, pos) - 1, d.nrows - 1);
-        const uint64_t src = d.vsrc[k] + (pos - d.voff[k]);
-        const uint32_t x = src < d.arena_top ? d.arena[src] : 0u;   // (a handle never leaves the arena)
-        w[b >> 2] |= x << (8 * (b & 3));
-    }
-    if (nb == 16 && d.wide16) {
-        *reinterpret_cast<uint4 *>(d.val_data + base) = make_uint4(w[0], w[1], w[2], w[3]);
-    } else {
-#pragma unroll
-        for (uint32_t b = 0; b < 16; b++)
-            if (b < nb) d.val_data[base + b] = (uint8_t)(w[b >> 2] >> (8 * (b & 3)));
     }
 }
 
@@ -300,7 +274,10 @@ extern "C" int corro_read_rows(corro_ctx *ctx, const corro_read_in *in, int mem,
         CORRO_HIP_TRY(hipMemsetAsync(d.voff, 0, 8, s));
         size_t t = vtemp;
         CORRO_TRY(prim_inclusive_scan_u32_u64(vtmp, &t, d.val_size, d.voff + 1, nrows, s));
-        if (vbytes) CORRO_LAUNCH(k_rd_values, grid_for((vbytes + 15) / 16), d);
+        if (vbytes) {
+            const ValGather g{nrows, vbytes, d.voff, d.vsrc, d.arena, d.arena_top, d.val_data, d.wide16};
+            CORRO_LAUNCH(k_gather_values, grid_for((vbytes + 15) / 16), g);
+        }
         CORRO_HIP_TRY(hipMemcpyAsync(out->val_off, o_voff, nrows * 8, back, s));
         st.down(out->val_size, d.val_size, nrows * 4);
         st.down(out->val_data, d.val_data, vbytes);

@@ -53,6 +53,54 @@ _READ_ROWS = tuple(("rows." + k, dt, "nrows") for k, dt in ROW_FIELDS.items())
 _READ_LONG = (("val_off", np.uint64, "nrows"), ("val_size", np.uint32, "nrows"), ("val_data", np.uint8, "val_data_len"))
 
 
+# corro_query_out: the per-row and per-cell arrays of pass 1
+_QUERY_ROWS = (("pk", np.uint64, "nrows"), ("cl", np.int64, "nrows"))
+_QUERY_CELLS = (("val_type", np.uint8, "ncells"), ("val_len", np.uint8, "ncells"), ("val0", np.uint64, "ncells"),
+                ("val1", np.uint64, "ncells"))
+_QUERY_LONG = (("val_off", np.uint64, "ncells"), ("val_size", np.uint32, "ncells"), ("val_data", np.uint8, "val_data_len"))
+_QUERY_TERMS = (("term_col", np.uint32), ("term_op", np.uint8), ("val_type", np.uint8), ("val_len", np.uint8),
+                ("val0", np.uint64), ("val1", np.uint64), ("const_off", np.uint64), ("const_size", np.uint32))
+
+
+def value_cell(v):
+    """A Python value (None, int, float, str, bytes) as the cell the engine stores: (val_type, val_len, val0,
+    val1, the bytes of a long value or None). TEXT / BLOB up to 16 bytes lie big-endian in val0 / val1; a
+    longer one has val_len VAL_LONG, its first 8 bytes in val0 and its bytes apart."""
+    if v is None:
+        return (5, 0, 0, 0, None)
+    if isinstance(v, (bool, int, np.integer)):
+        return (1, 0, int(v) & 0xFFFFFFFFFFFFFFFF, 0, None)
+    if isinstance(v, (float, np.floating)):
+        return (2, 0, int.from_bytes(np.float64(v).tobytes(), "little"), 0, None)
+    ty = 3 if isinstance(v, str) else 4
+    b = v.encode() if isinstance(v, str) else bytes(v)
+    if len(b) > 16:
+        return (ty, VAL_LONG, int.from_bytes(b[:8], "big"), 0, b)
+    p = b + b"\0" * (16 - len(b))
+    return (ty, len(b), int.from_bytes(p[:8], "big"), int.from_bytes(p[8:], "big"), None)
+
+
+def cell_value(ty, ln, v0, v1, raw=None):
+    """value_cell's inverse: the Python value of a stored cell (raw: a long value's bytes)."""
+    ty, ln, v0, v1 = int(ty), int(ln), int(v0) & 0xFFFFFFFFFFFFFFFF, int(v1) & 0xFFFFFFFFFFFFFFFF
+    if ty == 5:
+        return None
+    if ty == 1:
+        return v0 - (1 << 64) if v0 >> 63 else v0
+    if ty == 2:
+        return float(np.frombuffer(v0.to_bytes(8, "little"), np.float64)[0])
+    b = raw if ln == VAL_LONG else (v0.to_bytes(8, "big") + v1.to_bytes(8, "big"))[:ln]
+    return b.decode() if ty == 3 else bytes(b)
+
+
+def query_values(res):
+    """The cells of a host query_rows(values=True) result as Python values: one list per selected row."""
+    n, m = res["val_type"].shape
+    lv = res["long_values"]
+    return [[cell_value(res["val_type"][r, j], res["val_len"][r, j], res["val0"][r, j], res["val1"][r, j], lv.get(r * m + j))
+             for j in range(m)] for r in range(n)]
+
+
 def rows_as_batch(rows):
     """The rows of a read_rows(values=True) result as a batch apply() takes, in the same memory. Every
     array is passed as it is but cl: corro_rows carries it as int64, corro_changes as uint32."""
@@ -363,6 +411,87 @@ class MergeEngine:
                 res["long_values"] = {int(i): raw[int(off[i]):int(off[i]) + int(size[i])] for i in np.nonzero(size)[0]}
             else:
                 res["long_values"] = self.long_values(res)
+        return res
+
+    def query_prepare(self, table, where=(), columns=(), keys=None, values=True, device=False):
+        """corro_query_in for query_rows' arguments: (struct, arrays to keep alive, Mem, nkeys, nproj). The
+        arrays live where the keys do (numpy: host; CUDA tensors: device), or for the table form on the
+        host unless device is set. For a caller that runs the passes itself (bench_query.py)."""
+        t = self.table_index(table)
+        if not 0 <= t < len(self.schema):
+            raise L.CorroError(-4, f"no such table: {table}")
+        cols = self.schema[t][1]
+
+        def cid(c):
+            return 0 if c == "pk" else cols.index(c) + 1
+
+        q = {k: [] for k, _dt in _QUERY_TERMS}
+        group_off, data = [0], b""
+        for g in where:
+            for col, op, *v in g:
+                ty, ln, w0, w1, b = value_cell(v[0] if v else None)
+                q["term_col"].append(cid(col))
+                q["term_op"].append(L.QUERY_OPS[" ".join(op.lower().split())])
+                q["val_type"].append(ty), q["val_len"].append(ln), q["val0"].append(w0), q["val1"].append(w1)
+                q["const_off"].append(len(data)), q["const_size"].append(len(b) if b else 0)
+                data += b or b""
+            group_off.append(len(q["term_col"]))
+        q = {k: np.array(q[k], dt) for k, dt in _QUERY_TERMS}
+        q["group_off"] = np.array(group_off if where else [], np.uint32)
+        q["proj"] = np.array([cid(c) for c in columns], np.uint32)
+        q["const_data"] = np.frombuffer(data, np.uint8)
+        flags = (L.CORRO_QUERY_KEYED if keys is not None else 0) | (L.CORRO_QUERY_VALUES if values else 0)
+        dts = dict(_QUERY_TERMS + (("group_off", np.uint32), ("proj", np.uint32), ("const_data", np.uint8)))
+        q = {k: np.ascontiguousarray(a, dts[k]) for k, a in q.items()}
+        on_dev = _is_torch(keys) if keys is not None else bool(device)
+        mem = Mem((keys.device if keys is not None else f"cuda:{self.device}")) if on_dev else Mem()
+        if on_dev:
+            import torch
+            signed = {1: np.uint8, 4: np.int32, 8: np.int64}
+            q = {k: torch.from_numpy(a.view(signed[a.dtype.itemsize]).copy()).to(mem.dev) for k, a in q.items()}
+        s = L.QueryIn()
+        s.table, s.flags = t, flags
+        s.nterms, s.nproj = mem.count(q["term_col"]), mem.count(q["proj"])
+        s.ngroups = max(mem.count(q["group_off"]) - 1, 0)
+        s.const_data_len = mem.count(q["const_data"])
+        keep = mem.fill(s, q, [(k, dt, None) for k, dt in dts.items()])
+        nkeys = 0
+        if keys is not None:
+            nkeys = mem.count(keys)
+            keep += mem.fill(s, {"keys": keys}, (("keys", np.uint64, nkeys),))
+            s.nkeys = nkeys
+        return s, keep, mem, nkeys, int(s.nproj)
+
+    def query_rows(self, table, where=(), columns=(), keys=None, values=True, device=False):
+        """SELECT columns FROM table WHERE where over the live rows of the merged state (corro_query_rows).
+        where: a list of groups, each a list of (column name or "pk", op, Python value) -- ops = != <> < <=
+        > >= and (without a value) "is null" / "is not null"; a row is selected when every term of some
+        group holds, and an empty where selects every live row. columns: the projected names, "pk" for the
+        row key. The comparison is SQLite's, the constants converted by the columns' registered affinities
+        (set_column_types). keys=None: the whole table in ascending row key (numpy results; CUDA tensors
+        with device=True). keys: the keyed form over these row keys in request order -- a numpy array for
+        host results, a CUDA tensor for device results (only the totals reach the host).
+        Returns "nrows", "pk" and "cl" per selected row, the cells "val_type", "val_len", "val0", "val1"
+        shaped (nrows, nproj), for the keyed form "key_status" per key (0 absent, 1 selected, 2 deleted,
+        3 live but rejected) and "key_index" per row, and with values the long values' "val_off" /
+        "val_size" (per cell) / "val_data" and "val_data_len". Host results with values also carry
+        "long_values": {flat cell index: bytes} (query_values turns the cells into Python values)."""
+        s, keep, mem, nkeys, nproj = self.query_prepare(table, where, columns, keys, values, device)
+        keyed = bool(s.flags & L.CORRO_QUERY_KEYED)
+        tp = TwoPass(L.lib().corro_query_rows, (self._h, C.byref(s), mem.const), mem, L.QueryOut())
+        tp.run(0, (("key_status", np.uint8, nkeys),) if keyed else ())
+        tot = tp.totals(("nrows", "val_data_len"))
+        tot["ncells"] = tot["nrows"] * nproj
+        post = _QUERY_ROWS + _QUERY_CELLS + ((("key_index", np.uint32, "nrows"),) if keyed else ())
+        tp.run(1, post + (_QUERY_LONG if s.flags & L.CORRO_QUERY_VALUES else ()), tot)
+        del keep
+        res = {**tp.result(), **tot}
+        for k, _dt, size in _QUERY_CELLS + _QUERY_LONG[:2]:
+            if k in res:
+                res[k] = res[k].reshape(tot["nrows"], nproj)
+        if not mem.on_dev and "val_data" in res:
+            raw_bytes, off, size = res["val_data"].tobytes(), res["val_off"].reshape(-1), res["val_size"].reshape(-1)
+            res["long_values"] = {int(i): raw_bytes[int(off[i]):int(off[i]) + int(size[i])] for i in np.nonzero(size)[0]}
         return res
 
     def local_bound(self, kind, table, cell_off):

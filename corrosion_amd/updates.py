@@ -161,6 +161,26 @@ def read_candidates(engine, result, values=True):
     return engine.read_rows(result["cand_table"], result["cand_pk"], values=values)
 
 
+def query_candidates(engine, result, table, where=(), columns=(), values=True):
+    """Does a changed row still satisfy a subscription's WHERE: the keyed form of MergeEngine.query_rows over
+    the candidates of one table in a match_changes result, the step that follows read_candidates for a
+    subscription with a predicate. Returns query_rows' result (on the device when the match result is
+    there) and "cand_index": the candidate each key stands for, so key_status[j] (1 selected, 3 live but
+    rejected, 2 deleted, 0 absent) is the answer for candidate cand_index[j] and the selected rows carry
+    the projected columns."""
+    t = engine.table_index(table)
+    ct, pk = result["cand_table"], result["cand_pk"]
+    if _is_torch(pk):
+        idx = (ct == t).nonzero().reshape(-1)
+        keys = pk[idx].contiguous()
+    else:
+        idx = np.nonzero(np.asarray(ct) == t)[0]
+        keys = np.ascontiguousarray(np.asarray(pk)[idx])
+    res = engine.query_rows(t, where, columns, keys=keys, values=values)
+    res["cand_index"] = idx
+    return res
+
+
 def _host(a, dt):
     if _is_torch(a):
         a = a.cpu().numpy()

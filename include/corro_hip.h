@@ -303,7 +303,8 @@ int corro_ctx_set_values_autocompact(corro_ctx *ctx, uint64_t min_bytes);
 /* Stage timing with HIP events recorded on the engine's stream (for roofline reporting).
  * corro_last_timings returns milliseconds of the last apply per stage:
  * [0] k_hist [1] k_colscan [2] k_plan [3] k_scatter [4] k_merge [5] k_merge_ovf (0 if not run),
- * [6] / [7] the last need-diff or extraction count / fill pass, [8] the last extraction index build. */
+ * [6] / [7] the last need-diff or extraction count / fill pass, or pass 0 / pass 1 of the last
+ * corro_query_rows (first launch to last copy), [8] the last extraction index build. */
 int corro_ctx_set_profiling(corro_ctx *ctx, int on);
 int corro_last_timings(corro_ctx *ctx, float *ms, uint32_t cap, uint32_t *count);
 
@@ -1679,6 +1680,98 @@ int corro_local_write(corro_ctx *ctx, corro_bookie *bk, const uint8_t *actor_id,
  * the table's columns + 1, updates their cells, deletes 1. */
 int corro_local_bound(corro_ctx *ctx, const uint8_t *kind, const uint32_t *table, const uint64_t *cell_off, uint64_t nops,
                       uint64_t *bound);
+
+/* ------------------------------------------------------------------ query a table's live rows */
+
+/* SELECT <projection> FROM <table> WHERE <predicate> over the merged state: the body of api_v1_queries and
+ * build_query_rows_response (corro-agent/src/api/public/mod.rs:266, :468) for a predicate of column
+ * comparisons, and the initial fill of a subscription before corro_match_changes takes over. The rows come
+ * from the whole table (ascending row key: signed for a table keyed by its INTEGER pk, by id for an
+ * interned table) or, with CORRO_QUERY_KEYED, from keys[nkeys] (request order; a key listed k times is
+ * answered k times) -- the "does the changed row still satisfy the WHERE" step over corro_match_out.cand_pk.
+ *
+ * A row is live iff its causal length (cl, as corro_read_rows defines it) is odd; only live rows are
+ * selected. A column without a clock record reads as NULL. The predicate is an OR of AND-groups: group g
+ * holds terms [group_off[g], group_off[g + 1]), a row is selected when every term of some group is true
+ * (a group without terms is true) and ngroups == 0 selects every live row. Term k compares column
+ * term_col[k] (0: the row key, c: cid c) with the constant (val_type, val_len, val0, val1: the encoding of
+ * corro_changes, inline TEXT / BLOB bytes big-endian in val0 / val1; val_len CORRO_VAL_LONG: the bytes
+ * const_data[const_off[k], + const_size[k]), more than 16 and fewer than 2^24) by term_op[k].
+ *
+ * The comparison is SQLite's (tests/golden/query_kats.json pins it against SQLite 3.37.2;
+ * tests/query_model.py restates it): a comparison with NULL on either side is false and only IS NULL / IS
+ * NOT NULL see NULLs; numbers sort below TEXT below BLOB; INTEGER against REAL is compared exactly; TEXT and
+ * BLOB by their bytes, a prefix first. Before comparing, the constant of a term on cid c is converted by
+ * the column's registered affinity as a comparison converts it (numeric-looking TEXT becomes a number for an
+ * INTEGER, REAL or NUMERIC column, a number becomes its text for a TEXT column, a BLOB column converts
+ * nothing, and an INTEGER stays an INTEGER for a REAL column); under CORRO_AFF_POLICY_PORTABLE a constant
+ * whose conversion that policy refuses fails the call with CORRO_E_RANGE. A term on column 0 takes INTEGER
+ * affinity; on an interned table the key is an id, not a value, and such a term is CORRO_E_INVALID. The
+ * constant of IS NULL / IS NOT NULL is screened and otherwise ignored. Stored NaNs are out of scope.
+ *
+ * Output: per selected row pk and cl (and key_index, the index of the key it answers, in the keyed form);
+ * per cell, row-major nrows * nproj, the stored value of column proj[j] (0: the row key as the cell
+ * (INTEGER, 0, pk, 0); a column without a clock record: (NULL, 0, 0, 0); a long value's val1 is its arena
+ * handle, as in exports) and with CORRO_QUERY_VALUES its bytes at val_data[val_off[k], + val_size[k])
+ * (val_size 0 for any other cell). A column may be projected more than once; nproj == 0 is allowed.
+ * key_status (keyed form, pass 0): 0 absent, 1 selected, 2 deleted, 3 live but rejected by the predicate.
+ *
+ * Two passes: pass 0 fills key_status, nrows and val_data_len (0 without the flag); pass 1 computes them
+ * again and fills the rest; output arrays given as NULL are not written. `mem` (CORRO_MEM_HOST or
+ * CORRO_MEM_DEVICE) covers every array of both structs: with device memory only the totals and the error
+ * words cross PCIe. Synchronous on the context's stream. Nothing is written into the row store, the value
+ * arena or the intern table. Fails, before anything is written, with CORRO_E_INVALID for a NULL struct, a
+ * bad mem or pass, unknown flag bits, a required array that is NULL while its count is not 0 (keys;
+ * group_off; term_col, term_op, val_type, val_len, val0, val1; proj; key_status in pass 0; the const_
+ * arrays of a long constant; val_off, val_size, val_data of pass 1 with CORRO_QUERY_VALUES), a group_off
+ * that decreases or passes nterms, an op above 7, a val_type outside 1..5, a cid above the table's column
+ * count (term or projection), a malformed constant (an inline val_len above 16, a long one that is not TEXT
+ * or BLOB, has 16 bytes or fewer or leaves const_data), a REAL constant that is NaN, or pass-1 totals that
+ * differ from what the pass computes; CORRO_E_UNKNOWN_TABLE for a table index the schema does not have;
+ * CORRO_E_RANGE for more than CORRO_QUERY_MAX_TERMS terms, CORRO_QUERY_MAX_GROUPS groups or
+ * CORRO_QUERY_MAX_PROJ projected columns, nkeys >= 2^31 or nrows * max(nproj, 1) >= 2^32; CORRO_E_DEVICE
+ * for a poisoned context. An empty state, an empty table and nkeys == 0 answer with nrows = 0. */
+#define CORRO_QUERY_KEYED 1u
+#define CORRO_QUERY_VALUES 2u
+enum { CORRO_QOP_EQ = 0, CORRO_QOP_NE = 1, CORRO_QOP_LT = 2, CORRO_QOP_LE = 3, CORRO_QOP_GT = 4, CORRO_QOP_GE = 5,
+       CORRO_QOP_IS_NULL = 6, CORRO_QOP_IS_NOT_NULL = 7 };
+#define CORRO_QUERY_MAX_TERMS 64u
+#define CORRO_QUERY_MAX_GROUPS 64u
+#define CORRO_QUERY_MAX_PROJ 256u
+
+typedef struct {
+    uint32_t table;
+    uint32_t flags;                        /* CORRO_QUERY_KEYED | CORRO_QUERY_VALUES */
+    uint64_t nkeys;                        /* keyed form */
+    const uint64_t *keys;                  /* nkeys: row keys as in corro_changes.pk, e.g. corro_match_out.cand_pk */
+    uint32_t ngroups, nterms;
+    const uint32_t *group_off;             /* ngroups + 1 */
+    const uint32_t *term_col;              /* nterms: 0 the row key, c cid c */
+    const uint8_t *term_op;                /* nterms: CORRO_QOP_* */
+    const uint8_t *val_type, *val_len;     /* nterms: the constant, as a cell */
+    const uint64_t *val0, *val1;
+    const uint64_t *const_off;             /* nterms: long constants' bytes in const_data */
+    const uint32_t *const_size;
+    const uint8_t *const_data;
+    uint64_t const_data_len;
+    uint32_t nproj;
+    const uint32_t *proj;                  /* nproj: 0 the row key, c cid c */
+} corro_query_in;
+
+typedef struct {
+    uint64_t nrows, val_data_len;          /* pass 0 outputs, pass 1 inputs */
+    uint8_t *key_status;                   /* nkeys (pass 0, keyed form) */
+    uint32_t *key_index;                   /* nrows (pass 1, keyed form) */
+    uint64_t *pk;                          /* nrows (pass 1) */
+    int64_t *cl;                           /* nrows */
+    uint8_t *val_type, *val_len;           /* nrows * nproj, row-major */
+    uint64_t *val0, *val1;
+    uint64_t *val_off;                     /* nrows * nproj (CORRO_QUERY_VALUES) */
+    uint32_t *val_size;
+    uint8_t *val_data;                     /* val_data_len */
+} corro_query_out;
+
+int corro_query_rows(corro_ctx *ctx, const corro_query_in *in, int mem, corro_query_out *out, int pass);
 
 #ifdef __cplusplus
 }
