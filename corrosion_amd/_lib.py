@@ -51,6 +51,7 @@ EXPORTS = [
     "corro_process_fully_buffered_batch",
     "corro_local_write", "corro_local_bound", "corro_pk_count",
     "corro_query_rows",
+    "corro_sub_create", "corro_sub_destroy", "corro_sub_update", "corro_sub_rows", "corro_sub_last_timings",
 ]
 
 CORRO_CS_FULL, CORRO_CS_EMPTY, CORRO_CS_EMPTY_SET = 0, 1, 2
@@ -65,6 +66,8 @@ CORRO_QUERY_KEYED, CORRO_QUERY_VALUES = 1, 2  # corro_query_in.flags
 # corro_query_in.term_op (CORRO_QOP_*), by the SQL spelling MergeEngine.query_rows takes
 QUERY_OPS = {"=": 0, "==": 0, "!=": 1, "<>": 1, "<": 2, "<=": 3, ">": 4, ">=": 5, "is null": 6, "is not null": 7}
 CORRO_QUERY_MAX_TERMS, CORRO_QUERY_MAX_GROUPS, CORRO_QUERY_MAX_PROJ = 64, 64, 256
+CORRO_SUB_INSERT, CORRO_SUB_UPDATE, CORRO_SUB_DELETE = 0, 1, 2  # corro_sub_events.type
+CORRO_SUB_STAGES = 6  # corro_sub_last_timings
 
 
 class CorroError(RuntimeError):
@@ -351,6 +354,17 @@ class QueryOut(C.Structure):
         "key_status", "key_index", "pk", "cl", "val_type", "val_len", "val0", "val1", "val_off", "val_size", "val_data")]
 
 
+class SubEvents(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("nevents", "ninsert", "nupdate", "ndelete", "val_data_len")] + [
+        (k, C.c_void_p) for k in ("type", "rowid", "change_id", "pk", "val_type", "val_len", "val0", "val1", "val_off",
+                                  "val_size", "val_data")]
+
+
+class SubRowsOut(C.Structure):
+    _fields_ = [("nrows", C.c_uint64), ("val_data_len", C.c_uint64)] + [(k, C.c_void_p) for k in (
+        "rowid", "pk", "val_type", "val_len", "val0", "val1", "val_off", "val_size", "val_data")]
+
+
 _lib = None
 
 
@@ -480,6 +494,11 @@ def lib():
         "corro_local_bound": (i32, [vp, vp, vp, vp, u64, vp]),
         "corro_pk_count": (i32, [vp, u32, vp]),
         "corro_query_rows": (i32, [vp, C.POINTER(QueryIn), i32, C.POINTER(QueryOut), i32]),
+        "corro_sub_create": (i32, [vp, C.POINTER(QueryIn), i32, u64, u64, vp]),
+        "corro_sub_destroy": (None, [vp]),
+        "corro_sub_update": (i32, [vp, vp, u64, i32, C.POINTER(SubEvents), i32]),
+        "corro_sub_rows": (i32, [vp, i32, C.POINTER(SubRowsOut), i32]),
+        "corro_sub_last_timings": (i32, [vp, i32, vp, u32, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)

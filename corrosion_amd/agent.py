@@ -214,6 +214,7 @@ class Agent:
         self.bookie = Bookie()
         self.actor_id = actor_id
         self.site_ids = {}      # ordinal -> 16-byte site id (crsql_site_id)
+        self.last_match = None  # the last match_changes result (update_subscription's default input)
 
     def row_keys(self, changes, find_only=False):
         """Row keys of the changes' primary keys: an INTEGER pk is its own key; an interned table's
@@ -399,8 +400,19 @@ class Agent:
         frames' headers and the impact flags are read where they lie (util.rs:1026-1030). Returns
         updates.match_changes' result; cand_cs indexes the kept frames (dec["cs_dev"])."""
         from . import updates
-        return updates.match_changes(self.engine, dec["changes"], processed.impact, dec["cs_dev"], filters, device=True,
-                                     ncs=dec["n_dev"])
+        self.last_match = updates.match_changes(self.engine, dec["changes"], processed.impact, dec["cs_dev"], filters,
+                                                device=True, ncs=dec["n_dev"])
+        return self.last_match
+
+    def update_subscription(self, sub, cls, result=None):
+        """The stage behind match_changes: advance the subscription `sub` (updates.Subscription) by filter
+        class `cls`'s candidates of the last match_changes result (or `result`), on the device. Returns the
+        subscription's events (Subscription.update) as CUDA tensors."""
+        if result is None:
+            result = self.last_match
+            if result is None:
+                raise ValueError("update_subscription needs a match result: call match_changes first or pass result=")
+        return sub.handle_candidates(result, cls)
 
     def read_matched(self, processed, dec, filters, values=True):
         """match_changes, then the candidates' current rows (updates.read_candidates) where they lie: returns

@@ -10,9 +10,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libcorro_hip.so")
-SOURCES = ["engine.hip", "sync_needs.hip", "partition.hip", "prims.hip", "extract.hip", "wire.hip", "wire_encode.hip", "req_plan.hip", "req_decode.hip", "state_decode.hip", "state_encode.hip", "match.hip", "need_tails.hip", "answer_assemble.hip", "buffered_serve.hip", "bookie_image.hip", "row_read.hip", "query.hip", "ready_batch.hip", "local_write.hip", "booked.cpp", "agent.cpp",
+SOURCES = ["engine.hip", "sync_needs.hip", "partition.hip", "prims.hip", "extract.hip", "wire.hip", "wire_encode.hip", "req_plan.hip", "req_decode.hip", "state_decode.hip", "state_encode.hip", "match.hip", "need_tails.hip", "answer_assemble.hip", "buffered_serve.hip", "bookie_image.hip", "row_read.hip", "query.hip", "sub_view.hip", "ready_batch.hip", "local_write.hip", "booked.cpp", "agent.cpp",
            "pkeys.hip", "gaps.hip", "affinity.hip", "agent_dev.hip", "bufpool.hip", "values_compact.hip"]
-HEADERS = ["internal.h", "merge_kernels.h", "ovf_kernels.h", "ranges.h", "booked.h", "rowhash.h", "rowstore.h", "agent_dev.h", "scratch.h", "scratch_core.h", "search.h", "query_terms.h", "value_gather.h"]
+HEADERS = ["internal.h", "merge_kernels.h", "ovf_kernels.h", "ranges.h", "booked.h", "rowhash.h", "rowstore.h", "agent_dev.h", "scratch.h", "scratch_core.h", "search.h", "query_terms.h", "value_gather.h", "value_cmp.h"]
 ARCH = "gfx950"
 
 

@@ -732,6 +732,7 @@ void corro_ctx_destroy(corro_ctx *ctx) {
     for (DevBuf &b : ctx->d_read) b.release();
     ctx->d_ready.release();
     for (DevBuf &b : ctx->d_local) b.release();
+    for (DevBuf &b : ctx->d_sub) b.release();
     ctx->d_match_base.release();
     ctx->d_pkdir.release();
     ctx->d_pk_scratch.release();

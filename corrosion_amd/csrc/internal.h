@@ -185,6 +185,10 @@ __device__ inline uint32_t site_hash_find(const SiteHash &t, uint64_t lo, uint64
 int local_write_device(corro_ctx *ctx, const corro_local_in *in, int mem, corro_local_out *out,
                        int (*pre_commit)(void *, uint64_t), void *arg);
 
+// corro_query_rows (query.hip) for a caller inside the library whose arrays are all device memory: the
+// subscription store (sub_view.hip) runs its keyed selection and cell read through it.
+int query_rows_device(corro_ctx *ctx, const corro_query_in *in, corro_query_out *out, int pass);
+
 // the rocPRIM kernels' first-use cost paid once per process and device (prims.hip)
 int prims_warm(corro_ctx *ctx);
 // the agent's pinned host areas for a call of `ncs` changesets (agent_dev.hip), ahead of the first call
@@ -331,6 +335,11 @@ struct corro_ctx {
     // [1] the table form's sorted candidates and the sort's temp, [2] the per-cell value offsets and staged
     // host outputs
     corro::DevBuf d_query[3];
+    // subscription stores (sub_view.hip), one call at a time over every corro_sub of the context: [0] staged
+    // host keys, the sorted and the distinct keys and rocPRIM temp, [1] the keyed query's outputs, [2] the
+    // per-key classification, its scans and the event lists, [3] the per-cell sizes and offsets, [4] staged
+    // host outputs, [5] a rebuild's per-cell sizes and offsets
+    corro::DevBuf d_sub[6];
     corro::DevBuf d_match_base;   // u32 per table (+ 1): its first column slot
     bool match_base_ready = false;
     bool wire_schema_ready = false;

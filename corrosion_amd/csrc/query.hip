@@ -38,6 +38,7 @@
 #include "merge_kernels.h"
 #include "query_terms.h"
 #include "scratch.h"
+#include "value_cmp.h"
 #include "value_gather.h"
 
 namespace corro {
@@ -116,25 +117,6 @@ __device__ inline QCell row_cell(const RowStore &rs, const RowEnt &re, uint32_t 
     return {vtype(meta), vlen(meta), r->v0, r->v1};
 }
 
-// sqlite3IntFloatCompare: exact, no rounding of the integer (r is not NaN)
-__device__ inline int int_float_cmp(int64_t i, double r) {
-    if (r < -9223372036854775808.0) return 1;
-    if (r >= 9223372036854775808.0) return -1;
-    const int64_t y = (int64_t)r;
-    if (i < y) return -1;
-    if (i > y) return 1;
-    const double s = (double)i;
-    return s < r ? -1 : s > r ? 1 : 0;
-}
-
-__device__ inline int cmp_u64(uint64_t a, uint64_t b) { return a < b ? -1 : a > b ? 1 : 0; }
-
-// the top n bytes (1..8) of two big-endian words
-__device__ inline int cmp_top(uint64_t a, uint64_t b, uint32_t n) {
-    const uint32_t sh = 64 - 8 * n;
-    return cmp_u64(a >> sh, b >> sh);
-}
-
 // The order of a stored TEXT / BLOB cell and a constant of the same class: memcmp over the common prefix,
 // then the shorter first. The first 8 bytes come from v0 / w0 (a long value keeps its prefix there), bytes
 // 8..15 from v1 / w1 or, for a long stored value, from the arena; further bytes only on a tie that far,
@@ -170,21 +152,12 @@ __device__ int bytes_cmp(const QDev &d, const QCell &c, const QTerm &t) {
     return cmp_u64(la, lb);
 }
 
-__device__ inline uint32_t value_class(uint32_t ty) { return ty == CORRO_TEXT ? 1u : ty == CORRO_BLOB ? 2u : 0u; }
-
 // the order of two non-NULL values as SQLite compares them: numbers < TEXT < BLOB
 __device__ int value_cmp_sql(const QDev &d, const QCell &c, const QTerm &t) {
     const uint32_t ca = value_class(c.ty), cb = value_class(t.ty);
     if (ca != cb) return ca < cb ? -1 : 1;
     if (ca) return bytes_cmp(d, c, t);
-    if (c.ty == CORRO_INTEGER) {
-        if (t.ty == CORRO_INTEGER) return (int64_t)c.v0 < (int64_t)t.w0 ? -1 : (int64_t)c.v0 > (int64_t)t.w0 ? 1 : 0;
-        return int_float_cmp((int64_t)c.v0, __longlong_as_double((long long)t.w0));
-    }
-    const double a = __longlong_as_double((long long)c.v0);
-    if (t.ty == CORRO_INTEGER) return -int_float_cmp((int64_t)t.w0, a);
-    const double b = __longlong_as_double((long long)t.w0);
-    return a < b ? -1 : a > b ? 1 : 0;
+    return number_cmp(c.ty, c.v0, t.ty, t.w0);
 }
 
 __device__ bool term_true(const QDev &d, const RowEnt &re, const QTerm &t) {
@@ -345,6 +318,11 @@ __global__ void __launch_bounds__(256) k_q_cells(QDev d) {
 }  // namespace corro
 
 using namespace corro;
+
+// the device path for a caller inside the library (sub_view.hip): every array in device memory
+int corro::query_rows_device(corro_ctx *ctx, const corro_query_in *in, corro_query_out *out, int pass) {
+    return corro_query_rows(ctx, in, CORRO_MEM_DEVICE, out, pass);
+}
 
 extern "C" int corro_query_rows(corro_ctx *ctx, const corro_query_in *in, int mem, corro_query_out *out, int pass) {
     if (!ctx || !in || !out) return fail(CORRO_E_INVALID, "NULL argument");

@@ -240,3 +240,105 @@ def match_extracted(engine, rows, filters):
     imp = torch.ones(n, dtype=torch.uint8, device=dev)
     cs = torch.tensor([[0, n]], dtype=torch.int64, device=dev)
     return match_changes(engine, cols, imp, cs, filters, device=True)
+
+
+_SUB_TOTALS = ("nevents", "ninsert", "nupdate", "ndelete", "val_data_len")
+_SUB_EVENTS = (("type", np.uint8, "nevents"), ("rowid", np.uint64, "nevents"), ("change_id", np.uint64, "nevents"),
+               ("pk", np.uint64, "nevents"))
+_SUB_ROWS = (("rowid", np.uint64, "nrows"), ("pk", np.uint64, "nrows"))
+_SUB_CELLS = (("val_type", np.uint8, "ncells"), ("val_len", np.uint8, "ncells"), ("val0", np.uint64, "ncells"),
+              ("val1", np.uint64, "ncells"), ("val_off", np.uint64, "ncells"), ("val_size", np.uint32, "ncells"))
+_SUB_DATA = (("val_data", np.uint8, "val_data_len"),)
+INSERT = "Insert"
+EVENT_TYPES = (INSERT, UPDATE, DELETE)                 # by corro_sub_events.type
+
+
+class Subscription:
+    """One subscription's materialised result set on the device (corro_sub_create): SELECT columns FROM table
+    WHERE where, with MergeEngine.query_rows' spelling of where and columns (at least one column). The set is
+    filled from the table as it is now -- rowids 1..n in ascending row key, no events -- and advanced by
+    update / handle_candidates. row_cap (rows) and val_cap (bytes of long values) are starting sizes, 0 a
+    default; the store grows on its own. Close it before its engine."""
+
+    def __init__(self, engine, table, where=(), columns=(), row_cap=0, val_cap=0):
+        self.engine, self.table = engine, engine.table_index(table)
+        s, keep, mem, _nkeys, self.nproj = engine.query_prepare(table, where, columns, values=False)
+        h = C.c_void_p()
+        L.check(L.lib().corro_sub_create(engine._h, C.byref(s), mem.const, int(row_cap), int(val_cap), C.byref(h)))
+        del keep
+        self._h = h
+
+    def close(self):
+        if self._h:
+            L.lib().corro_sub_destroy(self._h)
+            self._h = None
+
+    def _shaped(self, res, rows, mem):
+        for k, _dt, _size in _SUB_CELLS:
+            res[k] = res[k].reshape(rows, self.nproj)
+        if not mem.on_dev:
+            raw, off, size = res["val_data"].tobytes(), res["val_off"].reshape(-1), res["val_size"].reshape(-1)
+            res["long_values"] = {int(i): raw[int(off[i]):int(off[i]) + int(size[i])] for i in np.nonzero(size)[0]}
+        return res
+
+    def two_pass(self, keys):
+        """The TwoPass of corro_sub_update over `keys`, for a caller that runs the passes itself (tests,
+        bench_sub.py), and the key array to keep alive."""
+        if not _is_torch(keys):
+            keys = np.ascontiguousarray(keys, np.uint64)
+        mem = Mem.of(keys)
+        a, p = mem.field(keys, np.uint64, "keys")
+        return TwoPass(L.lib().corro_sub_update, (self._h, p, mem.count(a), mem.const), mem, L.SubEvents()), a
+
+    def update(self, keys):
+        """Advance the set by the candidate row keys (corro_sub_update, both passes): a numpy array for host
+        results, a CUDA tensor for device results (only the totals reach the host). A key listed twice counts
+        once. Returns the events, first the Inserts and Updates in ascending row key, then the Deletes in
+        ascending rowid: "type" (0 Insert, 1 Update, 2 Delete), "rowid", "change_id" and "pk" per event, the
+        cells "val_type", "val_len", "val0", "val1", "val_off", "val_size" shaped (nevents, nproj), "val_data",
+        and the totals "nevents", "ninsert", "nupdate", "ndelete", "val_data_len". Host results also carry
+        "long_values": {flat cell index: bytes}."""
+        tp, keep = self.two_pass(keys)
+        tp.run(0)
+        tot = tp.totals(_SUB_TOTALS)
+        tot["ncells"] = tot["nevents"] * self.nproj
+        tp.run(1, _SUB_EVENTS + _SUB_CELLS + _SUB_DATA, tot)
+        del keep
+        return self._shaped({**tp.result(), **tot}, tot["nevents"], tp.mem)
+
+    def handle_candidates(self, result, cls):
+        """update over class `cls`'s candidates of this subscription's table in a match_changes result. On the
+        device the candidate columns stay there; the host reads the class's two offsets and, through the
+        table filter's nonzero(), the number of keys it keeps (one more synchronisation)."""
+        off = result["class_off"][cls:cls + 2]
+        a, b = (int(x) for x in (off.cpu().tolist() if _is_torch(off) else np.asarray(off).tolist()))
+        ct, pk = result["cand_table"][a:b], result["cand_pk"][a:b]
+        if _is_torch(pk):
+            keys = pk[(ct == self.table).nonzero().reshape(-1)].contiguous()
+        else:
+            keys = np.ascontiguousarray(np.asarray(pk)[np.asarray(ct) == self.table])
+        return self.update(keys)
+
+    STAGES = ("dedup", "query", "classify", "order_sizes", "fill_gather", "commit")
+
+    def last_timings(self):
+        """ms per stage of the last update, per pass ({0: {...}, 1: {...}}), taken while the engine's
+        set_profiling is on (corro_sub_last_timings): device events at the stage boundaries, the waits and
+        the host's reads of the totals between the kernels included. Pass 0 ends after "order_sizes"."""
+        out = {}
+        for which in (0, 1):
+            arr, n = (C.c_float * L.CORRO_SUB_STAGES)(), C.c_uint32()
+            L.check(L.lib().corro_sub_last_timings(self._h, which, arr, L.CORRO_SUB_STAGES, C.byref(n)))
+            out[which] = {self.STAGES[k]: float(arr[k]) for k in range(n.value)}
+        return out
+
+    def rows(self, device=False):
+        """The set in ascending rowid (corro_sub_rows): "nrows", "rowid" and "pk" per row, the cells shaped
+        (nrows, nproj) and the long values as in update; CUDA tensors with device=True."""
+        mem = Mem(f"cuda:{self.engine.device}") if device else Mem()
+        tp = TwoPass(L.lib().corro_sub_rows, (self._h, mem.const), mem, L.SubRowsOut())
+        tp.run(0)
+        tot = tp.totals(("nrows", "val_data_len"))
+        tot["ncells"] = tot["nrows"] * self.nproj
+        tp.run(1, _SUB_ROWS + _SUB_CELLS + _SUB_DATA, tot)
+        return self._shaped({**tp.result(), **tot}, tot["nrows"], mem)

@@ -1773,6 +1773,104 @@ typedef struct {
 
 int corro_query_rows(corro_ctx *ctx, const corro_query_in *in, int mem, corro_query_out *out, int pass);
 
+/* ------------------------------------------------------------------ a subscription's result set */
+
+/* The materialised result of one subscription, kept on the device and advanced by candidate row keys: what
+ * Matcher::handle_candidates (corro-types/src/pubsub.rs:1434-1709) keeps in its `query` table (one
+ * __corro_rowid per row) and emits as QueryEvent::Change(Insert | Update | Delete, RowId, cells, ChangeId).
+ * A subscription is what corro_query_rows expresses: one table, an OR of AND-groups of column comparisons,
+ * a projection of at least one column. The semantics are SQLite's for an upsert from `fresh EXCEPT current`
+ * and a delete from `current EXCEPT fresh` over an AUTOINCREMENT rowid (tests/golden/sub_kats.json pins them
+ * against SQLite 3.37.2; tests/sub_model.py restates them).
+ *
+ * corro_sub_create (the initial fill, pubsub.rs:1269-1432): runs `query` in its table form over the whole
+ * table; the selected rows enter the set in that form's order (ascending row key, signed for an INTEGER pk,
+ * by id for an interned table) with rowids 1..n. The rowid counter is then n, the last change id 0, and no
+ * event is emitted. The query's arrays (in `mem`'s memory) are copied: the caller may free them. row_cap
+ * (rows) and val_cap (bytes of long values) are starting sizes, 0 a default; the store grows on its own.
+ * A subscription belongs to its context, is used by one thread at a time with it, and is destroyed before it.
+ *
+ * corro_sub_update (handle_candidates, pubsub.rs:1434-1709): keys[nkeys] are candidate row keys, e.g. one
+ * class's corro_match_out.cand_pk of the subscription's table. A key listed more than once counts once;
+ * nkeys == 0 is a valid no-op. For each distinct key let `new` be its row under the keyed query (key_status
+ * 1, with its projected cells) or nothing (status 0, 2, 3) and `old` its row in the set or nothing:
+ *   nothing -> a row                      Insert, the new cells
+ *   a row   -> a row, the same cells      no event
+ *   a row   -> a row, some cell differs   Update, the new cells, the row's rowid
+ *   a row   -> nothing                    Delete, the old cells, the old rowid
+ *   nothing -> nothing                    no event
+ * so a change to a column that is not projected makes no event. Two cells are the same under SQLite's IS:
+ * NULL is NULL; INTEGER against REAL compares exactly (1 is 1.0, 2^53 + 1 is not 2^53 as REAL); -0.0 is 0.0;
+ * TEXT and BLOB of equal bytes differ; TEXT and BLOB compare by all their bytes, a long value by its bytes and
+ * never by its arena handle.
+ * Event order: first the Inserts and Updates together in ascending row key (the order above), then the
+ * Deletes in ascending rowid; change ids are consecutive in that order and continue from the previous
+ * call's last. Rowids are AUTOINCREMENT's under upsert: walking the Inserts and Updates in their order every
+ * event advances the counter by one, an Insert takes the counter's value, an Update keeps its row's rowid
+ * (the value it advanced past is never used); Deletes do not move the counter, and a row deleted and later
+ * selected again gets a fresh rowid.
+ * Events: per event type (0 Insert, 1 Update, 2 Delete), rowid, change_id and pk (the row key); per cell,
+ * row-major nevents * nproj, the cell as corro_query_rows gives it and a long value's bytes at
+ * val_data[val_off[k], + val_size[k]) (val_size 0 for any other cell; a long cell's val1 is a handle into the
+ * store's own arena, of no use to the caller).
+ *
+ * corro_sub_rows (all_rows, pubsub.rs:447): the set in ascending rowid: rowid, row key, cells, long bytes.
+ *
+ * Two passes, for update and rows: pass 0 writes only the totals (update: nevents, ninsert, nupdate,
+ * ndelete, val_data_len; rows: nrows, val_data_len) and changes nothing in the store; pass 1 computes
+ * everything again, checks the totals, fills the outputs (arrays given as NULL are not written) and, for
+ * update, commits the store. Pass-1 totals that differ from what the pass computes are CORRO_E_INVALID and
+ * leave the store unchanged. `mem` (CORRO_MEM_HOST or CORRO_MEM_DEVICE) covers every array: with device
+ * memory only the totals and the error words cross PCIe. Synchronous on the context's stream. Nothing is
+ * written into the row store, the value arena or the intern table; the store owns its long values' bytes
+ * (the engine's arena may be compacted between two calls).
+ * Fails, before anything is written, with CORRO_E_INVALID for a NULL argument, a bad mem or pass, a keyed
+ * query or unknown flag bits at create, nproj == 0, a keys array that is NULL while nkeys is not 0, a pass-1
+ * val_data that is NULL while val_data_len is not 0, and whatever corro_query_rows refuses in the query;
+ * with CORRO_E_RANGE for nkeys >= 2^31 or nevents * nproj (rows: nrows * nproj) >= 2^32; with CORRO_E_DEVICE
+ * for a poisoned context. */
+typedef struct corro_sub corro_sub;
+
+enum { CORRO_SUB_INSERT = 0, CORRO_SUB_UPDATE = 1, CORRO_SUB_DELETE = 2 };
+
+typedef struct {
+    uint64_t nevents, ninsert, nupdate, ndelete, val_data_len;  /* pass 0 outputs, pass 1 inputs */
+    uint8_t *type;                         /* nevents (pass 1): CORRO_SUB_* */
+    uint64_t *rowid;                       /* nevents */
+    uint64_t *change_id;                   /* nevents */
+    uint64_t *pk;                          /* nevents: the row key */
+    uint8_t *val_type, *val_len;           /* nevents * nproj, row-major */
+    uint64_t *val0, *val1;
+    uint64_t *val_off;                     /* nevents * nproj */
+    uint32_t *val_size;
+    uint8_t *val_data;                     /* val_data_len */
+} corro_sub_events;
+
+typedef struct {
+    uint64_t nrows, val_data_len;          /* pass 0 outputs, pass 1 inputs */
+    uint64_t *rowid;                       /* nrows (pass 1), ascending */
+    uint64_t *pk;                          /* nrows */
+    uint8_t *val_type, *val_len;           /* nrows * nproj, row-major */
+    uint64_t *val0, *val1;
+    uint64_t *val_off;                     /* nrows * nproj */
+    uint32_t *val_size;
+    uint8_t *val_data;                     /* val_data_len */
+} corro_sub_rows_out;
+
+int corro_sub_create(corro_ctx *ctx, const corro_query_in *query, int mem, uint64_t row_cap, uint64_t val_cap,
+                     corro_sub **out);
+void corro_sub_destroy(corro_sub *sub);
+int corro_sub_update(corro_sub *sub, const uint64_t *keys, uint64_t nkeys, int mem, corro_sub_events *out, int pass);
+int corro_sub_rows(corro_sub *sub, int mem, corro_sub_rows_out *out, int pass);
+/* Stage times of the subscription's last corro_sub_update of `pass`, in ms, taken while
+ * corro_ctx_set_profiling is on: events on the context's stream at the stage boundaries, so a stage holds
+ * its kernels, the waits between them and the host's read of its totals. Pass 0 has the first four stages,
+ * pass 1 all CORRO_SUB_STAGES: the key dedup; the keyed query (both its passes); the classification with its
+ * scans; the event order, the per-cell sizes and val_off; the append, the output fill, the gather and the
+ * download; the commit. *n = the number written (0: the call was not timed, or made no event). */
+#define CORRO_SUB_STAGES 6u
+int corro_sub_last_timings(corro_sub *sub, int pass, float *ms, uint32_t cap, uint32_t *n);
+
 #ifdef __cplusplus
 }
 #endif
